@@ -7,7 +7,14 @@ table + cube, PGS, chirp actions).  One step = one ``SOARM101Env.step()`` for
 every env = 10 physics substeps of 2 ms (``SOARM101_Env.py:39-40,131-132``).
 
     python bench.py [--gpus N --steps K --warmup W --config contact|nocontact|dr|rollout|mpc|mpc_dbkn|plumbing]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds the
+side measurements to that line: the per-kernel replay and roofline, the steps 20-120 steady window,
+the other constraint solver, the float64 oracle / fp32 CPU-backend baselines (each can be dropped
+again with its ``--no-*`` option).  ``--dump-outputs DIR`` writes what the last timed step computed
+as ``DIR/<name>.npy``.
 
 One process per GPU; envs shard by global env id (rank r owns
 [r*n, (r+1)*n)), there is no per-step collective (``scaling: weak``); the
@@ -46,6 +53,11 @@ def parse():
     p.add_argument("--ccd", default="mpr", choices=["native", "mpr"],
                    help="convex-convex narrowphase: MuJoCo's native GJK/EPA or libccd MPR")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--full", action="store_true",
+                   help="also run the side measurements (per-kernel replay + roofline, steady window, the other "
+                        "constraint solver, CPU baselines); without it only the timed window is run")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-profile", action="store_true")
@@ -271,6 +283,27 @@ def cpu_baseline(cfg_name, seconds, seed, solver="pgs", ccd="mpr"):
             "cpu_model": cpu_name, "nproc": os.cpu_count(), "mujoco": mj}
 
 
+DUMP_BYTES = 64 * 2**20
+
+
+def dump_outputs(path, outs, rank, seed, world=1):
+    """Write the arrays `outs` ({name: device tensor}) as path/<name>.npy (ranks > 0:
+    <name>.rank<r>.npy), float32 or float64, at most DUMP_BYTES in all over the `world` ranks: an
+    array over its equal share (of this rank's 1/world) is cut to a fixed sample of its flattened
+    elements (sorted indices drawn from `seed`)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // world // len(outs)
+    for k, v in outs.items():
+        a = v.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{k}.npy" if rank == 0 else f"{k}.rank{rank}.npy"), np.ascontiguousarray(a))
+
+
 def _mpc_net(seed, kind="DKUC"):
     """Random-init Koopman model of the reference's architecture (control/koopman.py): DKUC, or
     DBKN with its bilinear layer drawn N(0, 0.02^2) (the reference zero-initialises it, which
@@ -349,8 +382,11 @@ def main():
     # stay resident in HBM; a step then stages its row into the action buffer (one copy)
     acts = None
     if cfg["action"] in ("chirp", "random"):
+        # (rows past the timed window serve --full's steady window; the random stream's values depend
+        # on the shape drawn, so it keeps one shape whatever the options)
         t_in = max(args.warmup + args.steps, 120)
         if cfg["action"] == "chirp":
+            t_in = t_in if args.full else args.warmup + args.steps
             acts = torch.stack([W.chirp_action(tab, float(t), lib=torch) for t in range(t_in)]).contiguous()
         else:
             acts = torch.rand((t_in, n, 5), generator=gen, device=dev) - 0.5
@@ -483,14 +519,22 @@ def main():
     total_envs = n * world
     value = total_envs * args.steps / dt
     contacts = ncon / (total_envs * args.steps * 10)
+    if args.dump_outputs:
+        # before any replay below overwrites the state the last timed step left
+        outs = {"obs": sim.obs, "qpos": sim.qpos, "qvel": sim.qvel}
+        if rollout:  # (the action columns of the last row are never written)
+            outs.update(rollout_u=rows[:-1, :, :5], rollout_obs=rows[:, :, 5:], qstar=qstar)
+        if mpc:
+            outs["u_prev"] = run.u_prev
+        dump_outputs(args.dump_outputs, outs, rank, args.seed, world)
 
     # dominant kernel: HIP events (on the sim's stream) around every launch of a replay of
     # the timed region -- state, action stream and step index restored from the snapshot
     roof = None
-    costs = json.load(open(os.path.join(ROOT, "profiles", "algorithmic_cost.json")))
-    base = name if name in costs else "mpc"  # (mpc_dbkn: the same physics per env-step as mpc)
-    cost = costs.get(name if args.solver == "pgs" else f"{name}_newton", costs[base])
-    if not args.no_profile:
+    if args.full and not args.no_profile:
+        costs = json.load(open(os.path.join(ROOT, "profiles", "algorithmic_cost.json")))
+        base = name if name in costs else "mpc"  # (mpc_dbkn: the same physics per env-step as mpc)
+        cost = costs.get(name if args.solver == "pgs" else f"{name}_newton", costs[base])
         kp = args.steps
         restore_timed()
         t = snap_t
@@ -542,7 +586,7 @@ def main():
     # steady state: the same workload timed over env-steps 20..120 (from the reset), the window
     # where arm-cube / arm-table contacts are present (the driver's short window is not)
     steady = None
-    if not args.no_steady and not (rollout or mpc) and (args.warmup, args.steps) != (20, 100):
+    if args.full and not args.no_steady and not (rollout or mpc) and (args.warmup, args.steps) != (20, 100):
         restore_t0()
         t = 0
         for _ in range(20):
@@ -556,7 +600,7 @@ def main():
         sync()
         (dts,) = max_over_ranks(time.perf_counter() - ts)
         steady = {"window": "env-steps 20-120", "value": total_envs * 100 / dts, "ms_per_step": dts / 100 * 1e3}
-    elif (args.warmup, args.steps) == (20, 100):
+    elif args.full and (args.warmup, args.steps) == (20, 100):
         steady = {"window": "env-steps 20-120", "value": value, "ms_per_step": dt / args.steps * 1e3,
                   "note": "= the timed window"}
 
@@ -564,7 +608,7 @@ def main():
     # solver (BASELINE.json configs[2]); Newton is what the reference's MuJoCo runs by default
     # (its scene has no <option>), so both numbers are reported -- value is always --solver's
     other_solver = None
-    if not args.no_other_solver and name in ("contact", "dr"):
+    if args.full and not args.no_other_solver and name in ("contact", "dr"):
         other = "newton" if args.solver == "pgs" else "pgs"
         cm2 = W.model(name, solver=other, ccd=args.ccd)
         sim2 = BatchSim(cm2, n, gpu)
@@ -611,7 +655,7 @@ def main():
         del sim2, cm2
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(name, args.cpu_seconds, args.seed, args.solver, args.ccd)
 
     if rank == 0:

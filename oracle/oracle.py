@@ -1,7 +1,7 @@
 """ctypes wrapper of the float64 CPU oracle (``oracle/liboracle.so``).
 
 TEST INFRASTRUCTURE ONLY: imported by ``tests/``, ``__graft_entry__.smoke()``
-and ``bench.py``'s cpu_baseline leg as the checker.  The product path never
+and ``bench.py --full``'s cpu_baseline leg as the checker.  The product path never
 imports this module.  Parity against MuJoCo itself is *unpinned* (MuJoCo is
 absent and running the reference is denied); the oracle is
 pinned by analytic known-answer tests and the survey's FK anchors.

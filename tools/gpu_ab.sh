@@ -20,7 +20,8 @@ PY
 SOL=""
 [ "$S" != "PGS" ] && SOL="--solver newton"
 for v in "$@"; do
-  SOARM_SIM_LIB=tools/_ab/lib_$v.so timeout -k 10 300 python bench.py --no-cpu-baseline --no-other-solver $SOL > gpurun_out/ab_$v.json 2> gpurun_out/ab_$v.err || exit $?
-  SOARM_SIM_LIB=tools/_ab/lib_$v.so timeout -k 10 300 python bench.py --no-cpu-baseline --no-other-solver --no-steady $SOL --steps 20 --warmup 5 > gpurun_out/abd_$v.json 2>> gpurun_out/ab_$v.err || exit $?
-  python -c "import json,sys; d=json.loads(open('gpurun_out/ab_$v.json').read().strip().split(chr(10))[-1]); e=json.loads(open('gpurun_out/abd_$v.json').read().strip().split(chr(10))[-1]); print('$v', 'steady', round(d['value']), {k: round(x,4) for k,x in d['roofline']['kernel_ms_per_step'].items()}, 'driver', round(e['value']), {k: round(x,4) for k,x in e['roofline']['kernel_ms_per_step'].items()})"
+  BOUT=${BENCH_OUT:-bench_out}; mkdir -p $BOUT
+  SOARM_SIM_LIB=tools/_ab/lib_$v.so timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-other-solver $SOL > $BOUT/ab_$v.json 2> $BOUT/ab_$v.err || exit $?
+  SOARM_SIM_LIB=tools/_ab/lib_$v.so timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-other-solver --no-steady $SOL --steps 20 --warmup 5 > $BOUT/abd_$v.json 2>> $BOUT/ab_$v.err || exit $?
+  python -c "import json,sys; d=json.loads(open('$BOUT/ab_$v.json').read().strip().split(chr(10))[-1]); e=json.loads(open('$BOUT/abd_$v.json').read().strip().split(chr(10))[-1]); print('$v', 'steady', round(d['value']), {k: round(x,4) for k,x in d['roofline']['kernel_ms_per_step'].items()}, 'driver', round(e['value']), {k: round(x,4) for k,x in e['roofline']['kernel_ms_per_step'].items()})"
 done

@@ -16,6 +16,6 @@ if [ $rc -ne 0 ]; then grep -E "FAILED|Error|assert" $O/pytest_gpu.log | head -2
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { cat $O/smoke.log | tail -20; exit 1; }
 tail -4 $O/smoke.log
 for c in $CFGS; do
-  timeout -k 10 400 python bench.py --config $c --cpu-seconds 4 > $O/bench_$c.json 2> $O/bench_$c.err || { tail -20 $O/bench_$c.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --config $c --cpu-seconds 4 > $O/bench_$c.json 2> $O/bench_$c.err || { tail -20 $O/bench_$c.err; exit 1; }
   python -c "import json,sys; d=json.load(open('$O/bench_$c.json')); r=d['roofline'] or {}; print('$c', round(d['value']), 'env-steps/s', round(d['ms_per_step'],4), 'ms/step', r.get('kernel_ms_per_step'), 'cpu', d['cpu_baseline'] and round(d['cpu_baseline']['value']))"
 done

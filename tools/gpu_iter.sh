@@ -7,4 +7,5 @@ rc=$?
 echo "pytest rc=$rc" >> gpurun_out/pytest_gpu.log
 grep -E "passed|failed|FAILED|Error|assert" gpurun_out/pytest_gpu.log | tail -25
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 600 python bench.py --no-cpu-baseline > gpurun_out/bench_contact.json 2> gpurun_out/bench_contact.err && cat gpurun_out/bench_contact.json
+BOUT=${BENCH_OUT:-bench_out}; mkdir -p $BOUT
+timeout -k 10 600 python bench.py --full --no-cpu-baseline > $BOUT/bench_contact.json 2> $BOUT/bench_contact.err && cat $BOUT/bench_contact.json

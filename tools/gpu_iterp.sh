@@ -6,8 +6,9 @@ rc=$?
 echo "pytest rc=$rc" >> gpurun_out/pytest_gpu.log
 grep -E "passed|failed|Error|assert" gpurun_out/pytest_gpu.log | tail -8
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 600 python bench.py --no-cpu-baseline > gpurun_out/bench_contact.json 2> gpurun_out/bench_contact.err || exit $?
-python -c "import json; d=json.load(open('gpurun_out/bench_contact.json')); print('BENCH', round(d['value']), d['roofline']['kernel_ms_per_step'])"
+BOUT=${BENCH_OUT:-bench_out}; mkdir -p $BOUT
+timeout -k 10 600 python bench.py --full --no-cpu-baseline > $BOUT/bench_contact.json 2> $BOUT/bench_contact.err || exit $?
+python -c "import json; d=json.load(open('$BOUT/bench_contact.json')); print('BENCH', round(d['value']), d['roofline']['kernel_ms_per_step'])"
 timeout -k 10 300 python tools/phase_prof.py 120 > gpurun_out/phase.log 2>&1 || exit $?
 tail -3 gpurun_out/phase.log | python -c "
 import sys,json

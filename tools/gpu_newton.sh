@@ -12,7 +12,7 @@ grep -E "^E .*Assert" $O/pytest_newton.log | head -10
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 for args in "--solver newton --no-cpu-baseline" "--no-cpu-baseline"; do
   tag=$(echo $args | tr -d ' -' | cut -c1-40)
-  timeout -k 10 400 python bench.py $args > $O/bench_$tag.json 2> $O/bench_$tag.err || { tail -20 $O/bench_$tag.err; exit 1; }
+  timeout -k 10 400 python bench.py --full $args > $O/bench_$tag.json 2> $O/bench_$tag.err || { tail -20 $O/bench_$tag.err; exit 1; }
   python -c "import json; d=json.load(open('$O/bench_$tag.json')); r=d['roofline'] or {}; print('$args |', round(d['value']), 'env-steps/s', round(d['ms_per_step'],4), 'ms/step; kernel', r.get('kernel'), r.get('avg_launch_ms'), r.get('kernel_ms_per_step'))"
 done
 exit $rc
