@@ -34,7 +34,9 @@ struct CpuBatch {
   const sim_model* model = nullptr;
   int n = 0;
   DModel dm;                 // the model with host hull pointers
-  std::vector<float> sepax;  // separating-axis cache [pair*3+k][env] (soarm_collide.h SepCache)
+  // separating-axis cache [pair*3+k][env] (soarm_collide.h SepCache); mutable: each env's step
+  // updates its own column through the const batch
+  mutable std::vector<float> sepax;
 };
 
 namespace {
@@ -84,7 +86,7 @@ int collide_env(const CpuBatch& B, Sim<NA, NF>& S, int e, CpuContact* con, int& 
   float gpose[SIM_MAXBODY * BREC];
   float cbuf[PAIR_MAXCON * 7];
   write_body_frames(S, gpose, 1, 0, 0, 1);
-  float* sep = const_cast<float*>(B.sepax.data());
+  float* sep = B.sepax.data();
   int nc = 0;
   for (int p = 0; p < m.npair; p++) {
     PairOut o{cbuf, 1, 0, 0, m.pair_cap[p], 0};  // the pair's slots, re-based to this scratch

@@ -31,32 +31,6 @@
 
 namespace soarm {
 
-#ifdef SOARM_PHASE_PROF
-// diagnostic build: [0] solves (one lane per env), [1] sum of iterations, [2] sum of line-search
-// evaluations, [3] solves on the coupled (whole-problem) path, [4] sum of solve cycles, [5] max
-// solve cycles, [6] max iterations, [7] max line-search evaluations of one solve; split solves
-// (per env): [8] arm iterations, [9] arm evaluations, [10] free-body iterations, [11] free-body
-// evaluations; per wave: [12] waves, [13] sum over waves of the wave's max evaluations, [14] of
-// its max iterations, [15] sum of the wave's max solve cycles; per env (sum over both ranges):
-// [16] warm-start cycles, [17] Hessian + factor + solve cycles, [18] line-search cycles,
-// [19] cycles of the pass at the new point, [20] wave-max sum of [16], [21] of [17], [22] of [18],
-// [23] of [19]
-__device__ unsigned long long g_newton[24];
-#define NT_STAMP(k)                          \
-  {                                          \
-    const long long t_ = clock64();          \
-    ncyc[k] += t_ - nt_;                     \
-    nt_ = t_;                                \
-  }
-DEVI int wave_max_i(int v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-#else
-#define NT_STAMP(k)
-#endif
-
 template <int NA, int NF, bool CON>
 struct NewtonRows {
   static constexpr int NV = NA + 6 * NF;
@@ -86,24 +60,18 @@ struct NewtonRows {
   }
   static constexpr int hidx(int i, int j) { return i * (i + 1) / 2 + j; }  // packed lower, i >= j
 
-  // Quad mode (lpe() = 4 lanes per env): the env's contacts (and overflow rows) are split over
+  // Quad mode (QUAD_LPE = 4 lanes per env): the env's contacts (and overflow rows) are split over
   // its lanes, lane k taking contacts k, k+4, ...; the partial sums are combined by quad
   // butterflies (bit-identical on the 4 lanes), so every later step runs on identical values.
   // The dof rows (frictionloss, limits) are cheap and run on every lane.
-  static constexpr int QL = lpe<NF>();
-  static_assert(QL == 1 || QL == 4, "Newton lane split: 1 or 4 lanes per env");
-  DEVI int ql() const { return QL == 1 ? 0 : (L.lane & 3); }
-  static DEVI float qred(float x) {
-    if constexpr (QL == 4) return qsum(x);
-    else return x;
-  }
+  // (The contact-free k_step runs one lane per env and takes the same reductions, over 4
+  // neighbouring envs: DESIGN.md, known couplings.)
+  static constexpr int QL = QUAD_LPE;
+  DEVI int ql() const { return L.lane & 3; }
+  static DEVI float qred(float x) { return qsum(x); }
   static DEVI float qmaxf(float x) {
-    if constexpr (QL == 4) {
-      const float t = fmaxf(x, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0xB1, 0xF, 0xF, false)));
-      return fmaxf(t, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(t), 0x4E, 0xF, 0xF, false)));
-    } else {
-      return x;
-    }
+    const float t = fmaxf(x, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0xB1, 0xF, 0xF, false)));
+    return fmaxf(t, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(t), 0x4E, 0xF, 0xF, false)));
   }
   static DEVI float qminf(float x) { return -qmaxf(-x); }
 
@@ -226,16 +194,14 @@ struct NewtonRows {
       }
       // combine the quad's partial sums (skipped, wave-uniformly, when no lane has a row here:
       // every partial is then zero)
-      if constexpr (QL > 1) {
-        if (__any(mine)) {
-          cost = qred(cost);
-          if constexpr (C0) c0 = qred(c0);
+      if (__any(mine)) {
+        cost = qred(cost);
+        if constexpr (C0) c0 = qred(c0);
 #pragma unroll
-          for (int i = LO; i < HI; i++) jtf[i] = qred(jtf[i]);
-          if constexpr (WANT_H)
+        for (int i = LO; i < HI; i++) jtf[i] = qred(jtf[i]);
+        if constexpr (WANT_H)
 #pragma unroll
-            for (int k = 0; k < NH; k++) H[k] = qred(H[k]);
-        }
+          for (int k = 0; k < NH; k++) H[k] = qred(H[k]);
       }
     }
     if constexpr (LO == 0) {
@@ -379,9 +345,7 @@ struct NewtonRows {
           if (x < 0.f) c1 += x * v * D, c2 += v * v * D;
           if (v != 0.f) kink(-x0 * __builtin_amdgcn_rcpf(v), cl, cr_);
         }
-      if constexpr (QL > 1) {
-        if (__any(mine)) c1 = qred(c1), c2 = qred(c2), cl = qmaxf(cl), cr_ = qminf(cr_);
-      }
+      if (__any(mine)) c1 = qred(c1), c2 = qred(c2), cl = qmaxf(cl), cr_ = qminf(cr_);
       d1 += c1, d2 += c2, bl = fmaxf(bl, cl), br = fminf(br, cr_);
     }
     if constexpr (LO == 0) {
@@ -434,11 +398,8 @@ DEVI void mul_m(const Sim<NA, NF>& S, const float x[], float y[]) {
 template <int LO, int HI, int NA, int NF, bool CON>
 DEVI int newton_range(const Sim<NA, NF>& S, const NewtonRows<NA, NF, CON>& R, float a[], float jtf[], int& nls,
                       long long* ncyc) {
-#ifdef SOARM_PHASE_PROF
-  long long nt_ = clock64();
-#else
+  PROF_DECL(long long nt_ = clock64());  // (NT_STAMP: cycles since the last stamp into ncyc)
   (void)ncyc;
-#endif
   constexpr int NV = NA + 6 * NF, NR = HI - LO, NH = NR * (NR + 1) / 2;
   const DModel& m = *S.mp;
   const float scale = m.pgs_scale, tol = m.tolerance;
@@ -604,7 +565,7 @@ DEVI int newton_range(const Sim<NA, NF>& S, const NewtonRows<NA, NF, CON>& R, fl
     // rotational dofs of the cube (inertia 4.5e-6) have converged.  And exactness: a full
     // Newton step that leaves every row in its zone has minimised the one quadratic there.
     bool same = sig == sig0;  // every lane of the env: its rows kept their zones
-    if constexpr (NewtonRows<NA, NF, CON>::QL > 1) same = qsum(same ? 0.f : 1.f) == 0.f;
+    same = qsum(same ? 0.f : 1.f) == 0.f;
     if (scale * (-0.5f * al * dz) < tol || (same && fabsf(al - 1.f) < 1e-3f)) {
       it++;
       break;
@@ -643,10 +604,8 @@ DEVI int newton_solve(Sim<NA, NF>& S, const NewtonRows<NA, NF, CON>& R) {
   }
   int it, nls = 0;
   long long ncyc[4] = {0, 0, 0, 0};
-#ifdef SOARM_PHASE_PROF
-  const long long t0 = clock64();
-  int it_arm = 0, nls_arm = 0;
-#endif
+  PHASE_T(t0);
+  PROF_DECL(int it_arm = 0, nls_arm = 0);
   if constexpr (NF == 0) {
     it = newton_range<0, NV>(S, R, a, jtf, nls, ncyc);
   } else {
@@ -654,9 +613,7 @@ DEVI int newton_solve(Sim<NA, NF>& S, const NewtonRows<NA, NF, CON>& R) {
       it = newton_range<0, NV>(S, R, a, jtf, nls, ncyc);
     } else {
       it = newton_range<0, NA>(S, Rs, a, jtf, nls, ncyc);
-#ifdef SOARM_PHASE_PROF
-      it_arm = it, nls_arm = nls;
-#endif
+      PROF_DO(it_arm = it, nls_arm = nls);
       it += newton_range<NA, NV>(S, Rs, a, jtf, nls, ncyc);
     }
   }
@@ -670,40 +627,7 @@ DEVI int newton_solve(Sim<NA, NF>& S, const NewtonRows<NA, NF, CON>& R) {
     }
     S.zfin = z;
   }
-#ifdef SOARM_PHASE_PROF
-  {
-    // reduced over the wave first (one lane per env counts), then one atomic per counter and
-    // wave: per-env atomics on shared counters serialise in L2 and stall the waves being measured
-    const long long dt = clock64() - t0;
-    const bool one = (threadIdx.x & (lpe<NF>() - 1)) == 0;
-    auto wsum = [](double v) {
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-      return v;
-    };
-    const double sv[16] = {1.0, (double)it, (double)nls, (double)coupled, (double)dt, (double)it_arm,
-                           (double)nls_arm, (double)(it - it_arm), (double)(nls - nls_arm),
-                           (double)ncyc[0], (double)ncyc[1], (double)ncyc[2], (double)ncyc[3], 0.0, 0.0, 0.0};
-    const int sk[13] = {0, 1, 2, 3, 4, 8, 9, 10, 11, 16, 17, 18, 19};
-    for (int k = 0; k < 13; k++) {
-      const double w = wsum(one ? sv[k] : 0.0);
-      if ((threadIdx.x & 63) == 0) atomicAdd(&g_newton[sk[k]], (unsigned long long)w);
-    }
-    const int mx[4] = {wave_max_i((int)dt), wave_max_i(it), wave_max_i(nls), 0};
-    const int wc[4] = {wave_max_i((int)ncyc[0]), wave_max_i((int)ncyc[1]), wave_max_i((int)ncyc[2]),
-                       wave_max_i((int)ncyc[3])};
-    if ((threadIdx.x & 63) == 0) {
-      atomicMax(&g_newton[5], (unsigned long long)mx[0]);
-      atomicMax(&g_newton[6], (unsigned long long)mx[1]);
-      atomicMax(&g_newton[7], (unsigned long long)mx[2]);
-      atomicAdd(&g_newton[12], 1ull);
-      atomicAdd(&g_newton[13], (unsigned long long)mx[2]);
-      atomicAdd(&g_newton[14], (unsigned long long)mx[1]);
-      atomicAdd(&g_newton[15], (unsigned long long)mx[0]);
-      for (int k = 0; k < 4; k++) atomicAdd(&g_newton[20 + k], (unsigned long long)wc[k]);
-    }
-  }
-#endif
+  PROF_DO(prof_newton_end(t0, (threadIdx.x & (QUAD_LPE - 1)) == 0, it, nls, coupled, it_arm, nls_arm, ncyc));
 #pragma unroll
   for (int i = 0; i < NV; i++) S.qacc[i] = a[i], S.fcon[i] = jtf[i];
   return it;

@@ -30,46 +30,10 @@
 #include <utility>
 
 #include "soarm_collide.h"
+#include "soarm_prof.h"
 
 namespace soarm {
 
-#ifdef SOARM_PHASE_PROF
-// diagnostic build only: per-env PGS start/end clock, sweep count, fast-path flag (env < 65536)
-__device__ long long g_pgs_prof[65536 * 8];
-// fine-grained per-env clock stamps of one k_substep (diagnostic build): see k_substep
-__device__ long long g_stamp[65536 * 16];
-#define PSTAMP(k) \
-  if (e < 65536) g_stamp[16 * e + (k)] = clock64()
-// per-wave accumulators of k_substep's phase profile (layout: soarm_substep.h g_phase; [77..81] the
-// RS solve's split).  Lane 0 of each wave owns its row and launches are stream-ordered, so plain
-// read-modify-writes: shared-address atomics from every wave queued behind the profiled kernel's own
-// loads and inflated the phases after the solve ~15x (r05).  sim_phase_profile reduces the rows.
-// [82..84]: RS-kernel waves that took the v-form fallback -- count, max and summed wave cycles;
-// [85..91] lanes of such waves by cause (rs_why bits).
-constexpr int WPH = 92, WPH_MAXW = 16384;
-__device__ unsigned long long g_wphase[WPH_MAXW * WPH];
-#define WPH_ID() (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6)
-__device__ int g_rs_force11;  // (set from SOARM_RS_FORCE11 by the launch code)
-#define WPH_ADD(k, v) g_wphase[WPH_ID() * WPH + (k)] += (unsigned long long)(v)
-#define WPH_MAX(k, v) \
-  g_wphase[WPH_ID() * WPH + (k)] = max(g_wphase[WPH_ID() * WPH + (k)], (unsigned long long)(v))
-// contact-row build split: [0] loads + frame, [1] Jacobian, [2] Gram / M^-1 / velocities, [3] edges + LDS writes
-__device__ long long g_rowprof[65536 * 4];
-#define RP_INIT long long rp_acc[4] = {0, 0, 0, 0}, rp_t = clock64()
-#define RP_MARK(k)                  \
-  {                                 \
-    const long long t_ = clock64(); \
-    rp_acc[k] += t_ - rp_t;         \
-    rp_t = t_;                      \
-  }
-#define RP_STORE \
-  if (e < 65536) g_rowprof[4 * e] = rp_acc[0], g_rowprof[4 * e + 1] = rp_acc[1], g_rowprof[4 * e + 2] = rp_acc[2], g_rowprof[4 * e + 3] = rp_acc[3]
-#else
-#define PSTAMP(k)
-#define RP_INIT
-#define RP_MARK(k)
-#define RP_STORE
-#endif
 
 constexpr int LDS_CON = 6;  // contacts whose rows stay in LDS
 // Lanes per env of the contact substep kernel: 4 lanes run the same per-env code
@@ -78,14 +42,7 @@ constexpr int LDS_CON = 6;  // contacts whose rows stay in LDS
 // free body, the contact-space sweep of the cube block gives lane k ownership of block
 // contact k's residuals (its cross-Gram row), broadcast within the quad (DPP) on that
 // contact's turn.  The arm-only scene has no block; its quad splits the other parts.
-#ifndef SOARM_LPE
-#define SOARM_LPE 4
-#endif
-#ifndef SOARM_LPE_ARM
-#define SOARM_LPE_ARM 4
-#endif
-template <int NF>
-constexpr int lpe() { return NF == 1 ? SOARM_LPE : SOARM_LPE_ARM; }
+constexpr int QUAD_LPE = 4;
 // value of lane J of each quad (DPP quad_perm broadcast); J is a compile-time 0..3
 // projected Gauss-Seidel step of a pyramid edge, max(x, -f): one VOP3 max with a
 // negated source.  fmaxf(x, -f) on a loop-carried f costs an extra canonicalising
@@ -549,9 +506,7 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
   // Gram blocks / edge ARdiag nor the warm start below (rs_solve builds its own)
   bool rs_fast = false;
   int rs_nat = 0, rs_nct = 0, rs_nac = 0;  // contacts per category (RsLayout): arm-only, free body alone, both
-#ifdef SOARM_PHASE_PROF
-  int rs_why = 0;  // why a wave takes the fallback (bits: limit, overflow, order, CT>4, AT>1, AC>1, AT+AC)
-#endif
+  PROF_DECL(int rs_why = 0);  // why a wave takes the fallback (bits: limit, overflow, order, CT>4, AT>1, AC>1, AT+AC)
   // ---- dof frictionloss rows (MuJoCo row order: all of them first)
   float ff[NA], fa[NA], fR[NA], fhD[NA], fiD[NA];
 #pragma unroll
@@ -596,14 +551,10 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
   int ncon = 0;
   RP_INIT;
   // Contact row c from its collide output rw (dist, pos, normal geom1 -> geom2) and its pair's
-  // constants: record c (LDS, c < LDS_CON) or the overflow slab.  split: lane-split build
-  // (quad mode), the building lane writes the record into all 4 columns of its quad.
-  auto wrec = [&](int c, int f, float x, bool split) {
-    (void)split;  // the env's column is shared by its lanes: one store serves the quad
-    L.at(c, f) = x;
-  };
+  // constants: record c (LDS, c < LDS_CON) or the overflow slab.  The env's column is shared by
+  // its lanes, so the building lane's one store serves the quad.
   auto build_row = [&](int c, const float* rw, int b1, int b2, float mu, float tran, float margin, float KB0,
-                       float KB1, const float* si, bool split) {
+                       float KB1, const float* si) {
       const float cdist = rw[0];
       const float cpos[3] = {rw[1], rw[2], rw[3]};
       float fr[9] = {rw[4], rw[5], rw[6], 0, 0, 0, 0, 0, 0};
@@ -668,11 +619,11 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
 #pragma unroll
         for (int q = 0; q < 3; q++)
 #pragma unroll
-          for (int i = 0; i < NV; i++) wrec(c, 12 * q + i, jd[q][i], split);
-        wrec(c, F_MU, mu, split);
-        wrec(c, F_R, Rpy, split);
-        wrec(c, F_FLAGS, (float)flags, split);
-        if constexpr (NEWT) wrec(c, F_IARD, 1.f / Rpy, split);  // Newton: the pyramid's 1/R
+          for (int i = 0; i < NV; i++) L.at(c, 12 * q + i) = jd[q][i];
+        L.at(c, F_MU) = mu;
+        L.at(c, F_R) = Rpy;
+        L.at(c, F_FLAGS) = (float)flags;
+        if constexpr (NEWT) L.at(c, F_IARD) = 1.f / Rpy;  // Newton: the pyramid's 1/R
       }
       // Gram matrix G = [Jn; Jt1; Jt2] M^-1 [Jn; Jt1; Jt2]' and the three velocities:
       // every pyramid edge J_e = J_n + s J_tk (s = +-mu) follows from them.  Full
@@ -696,7 +647,7 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
       if (!NEWT && !rs_fast)
         if (lds) {
 #pragma unroll
-          for (int k2 = 0; k2 < 6; k2++) wrec(c, F_GRAM + k2, G[k2], split);
+          for (int k2 = 0; k2 < 6; k2++) L.at(c, F_GRAM + k2) = G[k2];
         }
       RP_MARK(2);
 #pragma unroll
@@ -708,10 +659,10 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
         const float ard = NEWT ? 0.f : G[0] + s * (2.f * (k2 ? G[2] : G[1]) + s * (k2 ? G[5] : G[3])) + Rpy;
         const float ar = -KB1 * vel - KB0 * imp * (cdist - margin);
         if (lds) {
-          wrec(c, F_AREF + ed, ar, split);
+          L.at(c, F_AREF + ed) = ar;
           if (!NEWT && !rs_fast) {
-            wrec(c, F_HARD + ed, 0.5f * ard, split);
-            wrec(c, F_IARD + ed, 1.f / ard, split);
+            L.at(c, F_HARD + ed) = 0.5f * ard;
+            L.at(c, F_IARD + ed) = 1.f / ard;
           }
         } else {
           const int r = 4 * c + ed;
@@ -727,9 +678,9 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
       }
   };
 
-  constexpr bool QUADR = lpe<NF>() == 4 && CON;
-  if constexpr (CON && QUADR) {
-    // per env (a soft reset's re-forward and the acc_bad retry list no contacts), so divergent
+  if constexpr (CON) {
+    // uniform over the launch: null only when the scene has no collide pass.  A soft reset's
+    // forward and the acc_bad retry list contacts too, the model's at qpos0 (qpos0_contacts).
     const bool listed = ccount != nullptr;
     // (RS) whether this env's rows fit a row-space layout; without a contact list the layouts hold
     // the NA frictionloss rows only, so an active limit row sends the wave to the v-form sweeps
@@ -775,23 +726,20 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
         // arm-only contact, (0, 1) plus one arm-cube contact, (1, 1) both, in one env or in two envs
         // of the wave (without it those waves -- ~1 launch in 10 over steps 20-120 -- took the v-form
         // sweeps at ~4x the wave time); other waves take the v-form sweeps
-#ifdef SOARM_PHASE_PROF
-        rs_why = (nlim > 0) | ((ncon > LDS_CON) << 1) | ((!ok && nlim == 0 && ncon <= LDS_CON) << 2) |
-                 ((rs_nct > 4) << 3) | ((rs_nat > 1) << 4) | ((rs_nac > 1) << 5);
-#endif
+        PROF_DO(rs_why = (nlim > 0) | ((ncon > LDS_CON) << 1) | ((!ok && nlim == 0 && ncon <= LDS_CON) << 2) |
+                         ((rs_nct > 4) << 3) | ((rs_nat > 1) << 4) | ((rs_nac > 1) << 5));
         rs_lane = ok && rs_nct <= 4 && rs_nat <= 1 && rs_nac <= 1;
       }
     }
     if constexpr (RS) {
-      // one vote of the whole wave, taken with every lane active (outside the per-env branch): the
-      // solve's dispatch on rs_fast is wave-uniform
+      // one vote of the wave's active lanes (outside the per-env branch): the solve's dispatch on
+      // rs_fast is wave-uniform.  In the acc_bad retry only the bad envs' lanes are active, an env's
+      // 16 lanes together, so the vote and the solve's row operations stay within whole envs.
       rs_fast = __all(rs_lane);
-#ifdef SOARM_PHASE_PROF
-      if (listed) rs_why |= (!rs_fast && rs_lane) << 6;  // an env that fits, in a wave with one that does not
-#endif
+      PROF_DO(if (listed) rs_why |= (!rs_fast && rs_lane) << 6);  // an env that fits, in a wave with one that does not
     }
     if (listed) {
-      auto build_listed = [&](int c, bool split) {
+      auto build_listed = [&](int c) {
         const int pk = __float_as_int(L.ex(c));
         const int p = pk >> 3, k = pk & 7;
         const int s0 = m.pair_slot[p];
@@ -802,56 +750,16 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
 #pragma unroll
         for (int q = 0; q < 5; q++) si[q] = m.pair_solimp[p][q];
         build_row(c, rw, m.pair_body1[p], m.pair_body2[p], S.fric >= 0.f ? S.fric : m.pair_friction[p],
-                  m.pair_tran[p], m.pair_margin[p], m.pair_KB[p][0], m.pair_KB[p][1], si, split);
+                  m.pair_tran[p], m.pair_margin[p], m.pair_KB[p][0], m.pair_KB[p][1], si);
       };
       const int nlds = ncon < LDS_CON ? ncon : LDS_CON;
       constexpr int SPL = RS ? 16 : 4;  // the RS kernel: the env's 16 lanes split the build
       for (int c0 = 0; c0 < nlds; c0 += SPL) {
         const int c = c0 + (L.lane & (SPL - 1));
-        if (c < nlds) build_listed(c, true);
+        if (c < nlds) build_listed(c);
       }
       wave_sync();  // the quad's records, written by its 4 lanes
-      for (int c = LDS_CON; c < ncon; c++) build_listed(c, false);
-    }
-  } else if constexpr (CON) {
-    if (ccount != nullptr) {
-      const int nw = (m.npair + 31) >> 5;
-#pragma unroll
-      for (int w = 0; w < PairMask::MAXW; w++) {  // unrolled: pm->w[] stays in registers
-        uint32_t bits = w >= nw ? 0u : pm.w[w];
-        while (bits) {
-          const int p = 32 * w + __builtin_ctz(bits);
-          bits &= bits - 1;
-          // everything this pair needs, loaded once and all in flight together: the count,
-          // the pair's constants and every slot it may fill (cap <= PAIR_MAXCON; a set mask
-          // bit means at least one contact, and slots past the count are never used)
-          RP_MARK(3);
-          const int cnt = pm.count(m, p);
-          const int s0 = m.pair_slot[p], cap = m.pair_cap[p];
-          const int b1 = m.pair_body1[p], b2 = m.pair_body2[p];
-          const float mu = S.fric >= 0.f ? S.fric : m.pair_friction[p];
-          const float tran = m.pair_tran[p], margin = m.pair_margin[p];
-          const float KB0 = m.pair_KB[p][0], KB1 = m.pair_KB[p][1];
-          float si[5];
-#pragma unroll
-          for (int q = 0; q < 5; q++) si[q] = m.pair_solimp[p][q];
-          float raw[PAIR_MAXCON][7];
-#pragma unroll
-          for (int k = 0; k < PAIR_MAXCON; k++)
-#pragma unroll
-            for (int f = 0; f < 7; f++) raw[k][f] = k < cap ? soa(cbuf, (s0 + k) * 7 + f, n, e) : 0.f;
-#pragma unroll
-          for (int k = 0; k < PAIR_MAXCON; k++) {
-            if (k >= cnt) break;
-            if (ncon >= SIM_MAXCON) {
-              S.status |= SIM_ST_CONOVERFLOW;
-              break;
-            }
-            build_row(ncon, raw[k], b1, b2, mu, tran, margin, KB0, KB1, si, false);
-            ncon++;
-          }
-        }
-      }
+      for (int c = LDS_CON; c < ncon; c++) build_listed(c);
     }
   }
   RP_MARK(3);
@@ -862,25 +770,17 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
 #pragma unroll
     for (int i = 0; i < NA; i++) fiR[i] = 1.f / fR[i];
     const NewtonRows<NA, NF, CON> nr{m, L, cr, fR, fiR, fa, nlim, nl, ncon};
-#ifdef SOARM_PHASE_PROF
-    if (e < 65536) g_pgs_prof[8 * e + 6] = g_pgs_prof[8 * e + 7] = g_pgs_prof[8 * e] = clock64();
+    PROF_DO(if (e < 65536) g_pgs_prof[8 * e + 6] = g_pgs_prof[8 * e + 7] = g_pgs_prof[8 * e] = clock64());
     PSTAMP(8);
     PSTAMP(9);  // (no separate warm-start phase: the solve below is stamp 9's phase and "pgs")
-#endif
     const int nit = newton_solve(S, nr);
-#ifdef SOARM_PHASE_PROF
-    if (e < 65536)
-      g_pgs_prof[8 * e + 1] = clock64(), g_pgs_prof[8 * e + 2] = nit, g_pgs_prof[8 * e + 3] = 0,
-                        g_pgs_prof[8 * e + 4] = nlim, g_pgs_prof[8 * e + 5] = ncon;
-#else
+    PROF_DO(if (e < 65536) g_pgs_prof[8 * e + 1] = clock64(), g_pgs_prof[8 * e + 2] = nit, g_pgs_prof[8 * e + 3] = 0,
+                           g_pgs_prof[8 * e + 4] = nlim, g_pgs_prof[8 * e + 5] = ncon);
     (void)nit;
-#endif
     return ncon;
   }
-#ifdef SOARM_PHASE_PROF
-  if (e < 65536) g_pgs_prof[8 * e + 6] = clock64();  // rows built
+  PROF_DO(if (e < 65536) g_pgs_prof[8 * e + 6] = clock64());  // rows built
   PSTAMP(8);
-#endif
 
   // ---- warm start from qacc_warmstart (forces implied by the primal), keep if it beats f = 0
   // (a wave on the RS solve makes its warm start in row space instead, rs_solve)
@@ -906,14 +806,14 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
     L.lm(l, L_FRC) = fs;
     add_arm_col(Mi, v, oh, sg * fs);
   }
-  // contacts (Gram form: J_e x = J_n x + s J_tk x; one M^-1 product per contact); quad mode:
-  // lane k takes contacts k, k+4, ... and the quad sums the velocity changes
+  // contacts (Gram form: J_e x = J_n x + s J_tk x; one M^-1 product per contact): lane k of
+  // the quad takes contacts k, k+4, ... and the quad sums the velocity changes
   float vw[NV];
 #pragma unroll
   for (int i = 0; i < NV; i++) vw[i] = 0.f;
   // (the RS kernel: the env's 16 lanes split the contacts, one each)
-  const int cstep = RS ? 16 : QUADR ? 4 : 1, cfirst = RS ? (L.lane & 15) : QUADR ? (L.lane & 3) : 0;
-  auto env_sum = [&](float x) { return RS ? rowsum16(x) : QUADR ? qsum(x) : x; };
+  const int cstep = RS ? 16 : CON ? 4 : 1, cfirst = RS ? (L.lane & 15) : CON ? (L.lane & 3) : 0;
+  auto env_sum = [&](float x) { return RS ? rowsum16(x) : CON ? qsum(x) : x; };
   for (int c = cfirst; c < nl; c += cstep) {
     float jn[NV], jt1[NV], jt2[NV];
 #pragma unroll
@@ -928,7 +828,7 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
       const float s = (ed & 1) ? -mu : mu;
       const float jar = jw[0] + s * jw[1 + (ed >> 1)] - L.at(c, F_AREF + ed);
       fs[ed] = jar < 0.f ? -jar / Rp : 0.f;
-      wrec(c, F_FRC + ed, fs[ed], QUADR);
+      L.at(c, F_FRC + ed) = fs[ed];
     }
     const float Dn = (fs[0] + fs[1]) + (fs[2] + fs[3]), D1 = mu * (fs[0] - fs[1]), D2 = mu * (fs[2] - fs[3]);
     float u[NV], w[NV];
@@ -962,7 +862,7 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
     const float sg = L.lm(l, L_SGN), f = L.lm(l, L_FRC), ar = L.lm(l, L_AREF);
     cost += 0.5f * f * (sg * pick<NA>(v, oh) - ar + L.lm(l, L_R) * f) + 0.5f * f * (sg * pick<NA>(S.qacc_s, oh) - ar);
   }
-  float ccost = 0.f;  // contacts' share (quad mode: lane k's contacts, summed over the quad)
+  float ccost = 0.f;  // contacts' share (lane k's contacts, summed over the quad)
   for (int c = cfirst; c < nl; c += cstep) {
     float jn[NV], jt1[NV], jt2[NV];
 #pragma unroll
@@ -983,7 +883,7 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
     }
   }
   cost += env_sum(ccost);
-  if constexpr (QUADR) wave_sync();  // F_FRC of the quad's contacts, written by their lanes
+  if constexpr (CON) wave_sync();  // F_FRC of the quad's contacts, written by their lanes
   for (int c = nl; c < ncon; c++)
     for (int ed = 0; ed < 4; ed++) {
       const int r = 4 * c + ed;
@@ -1009,9 +909,7 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
   }
   }
 
-#ifdef SOARM_PHASE_PROF
-  if (e < 65536) g_pgs_prof[8 * e + 7] = clock64();  // warm start + cost done
-#endif
+  PROF_DO(if (e < 65536) g_pgs_prof[8 * e + 7] = clock64());  // warm start + cost done
   // ---- projected Gauss-Seidel sweeps (mj_solPGS's improvement criterion, scaled by the model
   // constant 1 / (meaninertia * max(1, nv)), meaninertia = trace(M(qpos0)) / nv)
   const float scale = m.pgs_scale;
@@ -1039,11 +937,9 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
 #pragma unroll
     for (int i = 0; i < 3; i++) L.kp(k++) = S.ee[i];
   }
-#ifdef SOARM_PHASE_PROF
-  if (e < 65536) g_pgs_prof[8 * e] = clock64();
+  PROF_DO(if (e < 65536) g_pgs_prof[8 * e] = clock64());
   PSTAMP(9);
-  int nsweep = m.iterations, armstop = 0;
-#endif
+  PROF_DECL(int nsweep = m.iterations, armstop = 0);
   // dof-frictionloss rows (J = e_i): one pass.  Branch-free: a dof with frictionloss 0
   // (no row in MuJoCo) clamps to [0, 0] and stays an exact no-op.
   auto fric_rows = [&](float& improvement) {
@@ -1240,12 +1136,10 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
   for (int c = 0; c < c0; c++)
     if ((int)L.at(c, F_FLAGS) & TOUCH_FREE) npre = c0;
   const int npost = (c0 - npre) + (nl - c1);
-#ifdef SOARM_PHASE_PROF
-  bool npost_free = false;  // a non-block contact touches the free body
-  int nfree_x = 0;
-  for (int c = 0; c < nl; c++)
-    if ((c < c0 || c >= c1) && ((int)L.at(c, F_FLAGS) & TOUCH_FREE)) npost_free = true, nfree_x++;
-#endif
+  PROF_DECL(bool npost_free = false);  // a non-block contact touches the free body
+  PROF_DECL(int nfree_x = 0);
+  PROF_DO(for (int c = 0; c < nl; c++)
+            if ((c < c0 || c >= c1) && ((int)L.at(c, F_FLAGS) & TOUCH_FREE)) npost_free = true, nfree_x++);
   // the block's sweep (straight-line: one basic block with the friction rows)
   auto block_rows = [&](float& improvement) {
     if constexpr (NF == 1 && CON) {
@@ -1274,56 +1168,81 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
   // the post-block ones run (lanes without one use the zero record).
   const int ca = npost == 1 ? (c0 - npre > 0 ? npre : c1) : LDS_CON;
   auto xidx = [&](int j) { return j < c0 - npre ? npre + j : c1 + j - (c0 - npre); };  // j-th non-block contact
-  // ---- contact-space ("y") sweep of the register block, used when nothing else in the
-  // wave touches the free body (every lane: no limits, no overflow rows, no non-block
-  // contact other than at most one arm-only one).  Each block contact k keeps
-  // y_k = (J_n v, J_t1 v, J_t2 v) of the free body's velocity, shifted by its reference
-  // acceleration: a pyramid edge's aref is affine in the same directions,
-  // aref_e = alpha + s_e beta_k (s_e = +-mu), so res_e = (a - alpha) + s_e (t_k - beta_k)
-  // + R f_e.  A force step on contact j moves every other y_k by the 3x3 cross-Gram
-  // block J_k M^-1 J_j' (the free block of M is diagonal, host-validated) — 27 FMAs per
-  // contact instead of the three 6-dof dots and the 6-dof velocity update of the v form;
-  // the velocity is rebuilt once from the force change after the sweeps.  Same
-  // Gauss-Seidel sequence (MuJoCo's mj_solPGS row order) in exact arithmetic.
-  // Extra contact slot E of the y variants (every lane: at most one non-block contact,
-  // no limits, no overflow, at most 5 contacts): an arm-only contact, or one that touches
-  // the arm and the free body ("coupled"), or the zero record.  Its y_E lives in registers;
-  // its coefficients live in the LDS of records 5-6 (unused when no lane has more than 5
-  // contacts): W_E = M_arm^-1 J_E,arm' (how a force step on E moves v_arm, and how a
-  // frictionloss row moves y_E), the free-body cross-Gram blocks X_kE = J_k M^-1 J_E' with
-  // the block contacts, the off-diagonal edge Gram, the 3x3 Gram, 1/ARdiag, ARdiag/2, mu, R.
-  // Scratch of the extra slots (compile-time indices): the joint-limit list (no limit is
-  // active in the y variants) and an array of its own.
-  enum { E_W = 0, E_X = 18, E_A = 54, E_G = 60, E_IA = 66, E_HD = 70, E_MU = 74, E_RP = 75 };
-  // second extra slot F (an arm-only contact before E in row order), v-form on the arm:
-  // J_arm rows, W_F = M_arm^-1 J_F', edge Gram, 1/ARd, ARd/2, mu, R, aref shift, X_EF = J_E M^-1 J_F'
-  enum { F_J = 76, F_W = 94, F_A = 112, F_IA = 118, F_HD = 122, F_MUX = 126, F_RPX = 127, F_SH = 128, F_XE = 131,
-         XS_END = 140 };
-  static_assert(XS_END <= NA * LF + XS_EXT - XS_LIST, "extra-slot scratch fits");
-  auto EX = [&](int k) -> float& { return k < NA * LF ? L.lraw(k) : L.ex(XS_LIST + k - NA * LF); };
-  float yE[3] = {0.f, 0.f, 0.f}, fE[4] = {0.f, 0.f, 0.f, 0.f}, fF[4] = {0.f, 0.f, 0.f, 0.f};
-  // quad mode: the E/F coefficients preloaded into registers before the sweeps, in the
-  // register pairs the packed loop consumes (no memory reads inside the sweep loop)
-  struct ExtQ {
-    float muo, eA10, eA32, fA10, fA32, eMu, eRp, fMu, fRp, fJ2[6], fX2[3], eG2[3], xo[9], fSh2;
-    f2 eNia01, eNia23, fNia01, fNia23, eWp[9], eA2030, eA2131, fA2030, fA2131, eHD01, eHD23, fHD01, fHD23, fJp[6], fWp[9], fXp[3], eGp[3], qe01[3], qe23[3], fSh01;
-  } xq;
-  constexpr int NX = FC * (FC - 1) / 2;
-  float yb[FC][3], xg[NX > 0 ? NX : 1][9];
-  constexpr bool QUAD = lpe<NF>() == 4 && NF == 1 && CON && FC == 4;
-  const int sub = QUAD ? (L.lane & 3) : 0;
-  // quad mode: this lane's block contact (sub) — its y and its cross-Gram row X_sub,j
-  // (j = sub: the contact's own 3x3 Gram block), full 3x3 per j
-  float yo[3] = {0.f, 0.f, 0.f}, xr[QUAD ? FC : 1][9];
-  // quad mode, packed: this lane's contact's 4 edge residuals r_e = y_0 + s_e y_t(e) + R f_e
-  // (pairs (r0, r1), (r2, r3)), held scaled by -1/ARdiag_e (see sA10 below); the sweep
-  // broadcasts them instead of y
-  f2 ro01 = f2{0.f, 0.f}, ro23 = f2{0.f, 0.f};
-  // rows of the arm block of M^-1 as dof pairs (packed v_arm updates of the friction rows)
-  f2 Mp[NA][NA / 2];
-  auto ypair = [](int j, int k) { return j * FC - j * (j + 1) / 2 + (k - j - 1); };  // j < k
-  auto yblock_setup = [&]() {
-    if constexpr (NF == 1 && CON) {
+  auto sweeps = [&](auto first) {
+    for (int it = 0; it < m.iterations; it++) {
+      float improvement = 0.f;
+      if constexpr (decltype(first)::value) {
+        fric_rows(improvement);  // same basic block as the register block: they interleave
+        block_rows(improvement);
+        limit_rows(improvement);
+        for (int j = 0; j < npost; j++) lds_contact(j < c0 - npre ? npre + j : c1 + j - (c0 - npre), improvement);
+        scratch_rows(improvement);
+      } else {
+        fric_rows(improvement);
+        limit_rows(improvement);
+        for (int c = 0; c < npre; c++) lds_contact(c, improvement);
+        block_rows(improvement);
+        for (int j = 0; j < npost; j++) lds_contact(j < c0 - npre ? npre + j : c1 + j - (c0 - npre), improvement);
+        scratch_rows(improvement);
+      }
+      if (improvement * scale < m.tolerance) {
+        PROF_DO(nsweep = it + 1);
+        break;
+      }
+    }
+  };
+  PROF_DECL(bool pf_ypure = false, pf_yext = false, pf_yext2 = false, pf_ycoupled = false);  // (the y-form votes, for the profile record)
+  // The free-body contact scene has two more solvers, the y-form block sweeps and (RS kernel) the
+  // row-space solve; every other scene goes straight to the v-form sweeps above.
+  if constexpr (NF == 1 && CON) {
+    // ---- contact-space ("y") sweep of the register block, used when nothing else in the
+    // wave touches the free body (every lane: no limits, no overflow rows, no non-block
+    // contact other than at most one arm-only one).  Each block contact k keeps
+    // y_k = (J_n v, J_t1 v, J_t2 v) of the free body's velocity, shifted by its reference
+    // acceleration: a pyramid edge's aref is affine in the same directions,
+    // aref_e = alpha + s_e beta_k (s_e = +-mu), so res_e = (a - alpha) + s_e (t_k - beta_k)
+    // + R f_e.  A force step on contact j moves every other y_k by the 3x3 cross-Gram
+    // block J_k M^-1 J_j' (the free block of M is diagonal, host-validated) — 27 FMAs per
+    // contact instead of the three 6-dof dots and the 6-dof velocity update of the v form;
+    // the velocity is rebuilt once from the force change after the sweeps.  Same
+    // Gauss-Seidel sequence (MuJoCo's mj_solPGS row order) in exact arithmetic.
+    // Extra contact slot E of the y variants (every lane: at most one non-block contact,
+    // no limits, no overflow, at most 5 contacts): an arm-only contact, or one that touches
+    // the arm and the free body ("coupled"), or the zero record.  Its y_E lives in registers;
+    // its coefficients live in the LDS of records 5-6 (unused when no lane has more than 5
+    // contacts): W_E = M_arm^-1 J_E,arm' (how a force step on E moves v_arm, and how a
+    // frictionloss row moves y_E), the free-body cross-Gram blocks X_kE = J_k M^-1 J_E' with
+    // the block contacts, the off-diagonal edge Gram, the 3x3 Gram, 1/ARdiag, ARdiag/2, mu, R.
+    // Scratch of the extra slots (compile-time indices): the joint-limit list (no limit is
+    // active in the y variants) and an array of its own.
+    enum { E_W = 0, E_X = 18, E_A = 54, E_G = 60, E_IA = 66, E_HD = 70, E_MU = 74, E_RP = 75 };
+    // second extra slot F (an arm-only contact before E in row order), v-form on the arm:
+    // J_arm rows, W_F = M_arm^-1 J_F', edge Gram, 1/ARd, ARd/2, mu, R, aref shift, X_EF = J_E M^-1 J_F'
+    enum { F_J = 76, F_W = 94, F_A = 112, F_IA = 118, F_HD = 122, F_MUX = 126, F_RPX = 127, F_SH = 128, F_XE = 131,
+           XS_END = 140 };
+    static_assert(XS_END <= NA * LF + XS_EXT - XS_LIST, "extra-slot scratch fits");
+    auto EX = [&](int k) -> float& { return k < NA * LF ? L.lraw(k) : L.ex(XS_LIST + k - NA * LF); };
+    float yE[3] = {0.f, 0.f, 0.f}, fE[4] = {0.f, 0.f, 0.f, 0.f}, fF[4] = {0.f, 0.f, 0.f, 0.f};
+    // quad mode: the E/F coefficients preloaded into registers before the sweeps, in the
+    // register pairs the packed loop consumes (no memory reads inside the sweep loop)
+    struct ExtQ {
+      float muo, eA10, eA32, fA10, fA32, eMu, eRp, fMu, fRp, fJ2[6], fX2[3], eG2[3], xo[9], fSh2;
+      f2 eNia01, eNia23, fNia01, fNia23, eWp[9], eA2030, eA2131, fA2030, fA2131, eHD01, eHD23, fHD01, fHD23, fJp[6], fWp[9], fXp[3], eGp[3], qe01[3], qe23[3], fSh01;
+    } xq;
+    constexpr int NX = FC * (FC - 1) / 2;
+    float yb[FC][3], xg[NX][9];
+    const int sub = L.lane & 3;
+    // quad mode: this lane's block contact (sub) — its y and its cross-Gram row X_sub,j
+    // (j = sub: the contact's own 3x3 Gram block), full 3x3 per j
+    float yo[3] = {0.f, 0.f, 0.f}, xr[FC][9];
+    // quad mode, packed: this lane's contact's 4 edge residuals r_e = y_0 + s_e y_t(e) + R f_e
+    // (pairs (r0, r1), (r2, r3)), held scaled by -1/ARdiag_e (see sA10 below); the sweep
+    // broadcasts them instead of y
+    f2 ro01 = f2{0.f, 0.f}, ro23 = f2{0.f, 0.f};
+    // rows of the arm block of M^-1 as dof pairs (packed v_arm updates of the friction rows)
+    f2 Mp[NA][NA / 2];
+    auto ypair = [](int j, int k) { return j * FC - j * (j + 1) / 2 + (k - j - 1); };  // j < k
+    auto yblock_setup = [&]() {
 #pragma unroll
       for (int k = 0; k < FC; k++) {
         const int c = cslot[k];
@@ -1365,53 +1284,49 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
             }
           }
         }
-      if constexpr (QUAD) {
 #pragma unroll
-        for (int q = 0; q < 3; q++) yo[q] = sub == 0 ? yb[0][q] : sub == 1 ? yb[1][q] : sub == 2 ? yb[2][q] : yb[3][q];
+      for (int q = 0; q < 3; q++) yo[q] = sub == 0 ? yb[0][q] : sub == 1 ? yb[1][q] : sub == 2 ? yb[2][q] : yb[3][q];
 #pragma unroll
-        for (int j = 0; j < FC; j++)
+      for (int j = 0; j < FC; j++)
 #pragma unroll
-          for (int r = 0; r < 3; r++)
+        for (int r = 0; r < 3; r++)
 #pragma unroll
-            for (int q = 0; q < 3; q++) {
-              float cand[FC];
+          for (int q = 0; q < 3; q++) {
+            float cand[FC];
 #pragma unroll
-              for (int k = 0; k < FC; k++) {
-                if (k == j) {  // own Gram block, symmetric packed (nn, n1, n2, 11, 12, 22)
-                  const int lo = r < q ? r : q, hi = r < q ? q : r;
-                  const int gi = lo == 0 ? hi : (lo == 1 ? 2 + hi : 5);
-                  cand[k] = L.at(cslot[k], F_GRAM + gi);
-                } else {
-                  cand[k] = k < j ? xg[ypair(k, j)][3 * r + q] : xg[ypair(j, k)][3 * q + r];
-                }
+            for (int k = 0; k < FC; k++) {
+              if (k == j) {  // own Gram block, symmetric packed (nn, n1, n2, 11, 12, 22)
+                const int lo = r < q ? r : q, hi = r < q ? q : r;
+                const int gi = lo == 0 ? hi : (lo == 1 ? 2 + hi : 5);
+                cand[k] = L.at(cslot[k], F_GRAM + gi);
+              } else {
+                cand[k] = k < j ? xg[ypair(k, j)][3 * r + q] : xg[ypair(j, k)][3 * q + r];
               }
-              xr[j][3 * r + q] = sub == 0 ? cand[0] : sub == 1 ? cand[1] : sub == 2 ? cand[2] : cand[3];
             }
-      }
-    }
-  };
-  // per-sweep constants of the block in registers: 1/ARdiag, ARdiag/2, mu, R, the
-  // off-diagonal edge-Gram entries A_ed = J_e M^-1 J_d' (d < e) and the 3x3 Gram block
-  float yia[FC][4], yhd[FC][4], ymu[FC], yRp[FC], yA[FC][6], yG[FC][6];
-  // quad mode, packed: edge-Gram pairs (A20, A30), (A21, A31), ARdiag/2 pairs, and the own
-  // residuals' update per edge of contact j: C_e'e = (1, s'_e' on t(e')) X_sub,j (1, s_e on
-  // t(e)) + R delta (own contact), as pairs over e': r_own += C_.e df_e
-  f2 qA2030[FC], qA2131[FC], qhd01[FC], qhd23[FC], C01[QUAD ? FC : 1][4], C23[QUAD ? FC : 1][4];
-  // quad mode, packed: the residuals are carried scaled, s_e = -r_e / ARdiag_e, so the projected
-  // step is df = max(s_e, -f_e) with no multiply on the chain; the edge-Gram entries that move
-  // a later edge e' are pre-scaled by -1/ARdiag_e' (sA10 = -A10/ARdiag1, sA32, qA2030, qA2131)
-  float sA10[FC], sA32[FC];
-  // this lane's own block contact (quad mode): -1/ARdiag of its 4 edges as pairs
-  auto own_nia01 = [&]() {
-    return f2{-(sub == 0 ? yia[0][0] : sub == 1 ? yia[1][0] : sub == 2 ? yia[2][0] : yia[3][0]),
-              -(sub == 0 ? yia[0][1] : sub == 1 ? yia[1][1] : sub == 2 ? yia[2][1] : yia[3][1])};
-  };
-  auto own_nia23 = [&]() {
-    return f2{-(sub == 0 ? yia[0][2] : sub == 1 ? yia[1][2] : sub == 2 ? yia[2][2] : yia[3][2]),
-              -(sub == 0 ? yia[0][3] : sub == 1 ? yia[1][3] : sub == 2 ? yia[2][3] : yia[3][3])};
-  };
-  auto yblock_consts = [&](auto pk) {
-    if constexpr (NF == 1 && CON) {
+            xr[j][3 * r + q] = sub == 0 ? cand[0] : sub == 1 ? cand[1] : sub == 2 ? cand[2] : cand[3];
+          }
+    };
+    // per-sweep constants of the block in registers: 1/ARdiag, ARdiag/2, mu, R, the
+    // off-diagonal edge-Gram entries A_ed = J_e M^-1 J_d' (d < e) and the 3x3 Gram block
+    float yia[FC][4], yhd[FC][4], ymu[FC], yRp[FC], yA[FC][6];
+    // quad mode, packed: edge-Gram pairs (A20, A30), (A21, A31), ARdiag/2 pairs, and the own
+    // residuals' update per edge of contact j: C_e'e = (1, s'_e' on t(e')) X_sub,j (1, s_e on
+    // t(e)) + R delta (own contact), as pairs over e': r_own += C_.e df_e
+    f2 qA2030[FC], qA2131[FC], qhd01[FC], qhd23[FC], C01[FC][4], C23[FC][4];
+    // quad mode, packed: the residuals are carried scaled, s_e = -r_e / ARdiag_e, so the projected
+    // step is df = max(s_e, -f_e) with no multiply on the chain; the edge-Gram entries that move
+    // a later edge e' are pre-scaled by -1/ARdiag_e' (sA10 = -A10/ARdiag1, sA32, qA2030, qA2131)
+    float sA10[FC], sA32[FC];
+    // this lane's own block contact (quad mode): -1/ARdiag of its 4 edges as pairs
+    auto own_nia01 = [&]() {
+      return f2{-(sub == 0 ? yia[0][0] : sub == 1 ? yia[1][0] : sub == 2 ? yia[2][0] : yia[3][0]),
+                -(sub == 0 ? yia[0][1] : sub == 1 ? yia[1][1] : sub == 2 ? yia[2][1] : yia[3][1])};
+    };
+    auto own_nia23 = [&]() {
+      return f2{-(sub == 0 ? yia[0][2] : sub == 1 ? yia[1][2] : sub == 2 ? yia[2][2] : yia[3][2]),
+                -(sub == 0 ? yia[0][3] : sub == 1 ? yia[1][3] : sub == 2 ? yia[2][3] : yia[3][3])};
+    };
+    auto yblock_consts = [&]() {
 #pragma unroll
       for (int k = 0; k < FC; k++) {
         const int c = cslot[k];
@@ -1420,10 +1335,7 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
         ymu[k] = L.at(c, F_MU), yRp[k] = L.at(c, F_R);
         float G[6];
 #pragma unroll
-        for (int i = 0; i < 6; i++) {
-          G[i] = L.at(c, F_GRAM + i);
-          if constexpr (!QUAD) yG[k][i] = G[i];  // quad mode: the own block sits in xr
-        }
+        for (int i = 0; i < 6; i++) G[i] = L.at(c, F_GRAM + i);  // (the own block sits in xr)
         // edge e = J_n + s_e J_t(e): s = +mu, -mu, +mu, -mu; t = 1, 1, 2, 2
         const float mu = ymu[k];
         auto gt = [&](int e) { return (e >> 1) ? G[2] : G[1]; };                  // G_n,t(e)
@@ -1438,14 +1350,12 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
 #pragma unroll
           for (int d = 0; d < ed; d++)
             yA[k][q++] = G[0] + sg(ed) * gt(ed) + sg(d) * gt(d) + sg(ed) * sg(d) * gtt(ed, d);
-        if constexpr (QUAD && decltype(pk)::value) {
-          sA10[k] = -yia[k][1] * yA[k][0], sA32[k] = -yia[k][3] * yA[k][5];
-          qA2030[k] = f2{-yia[k][2] * yA[k][1], -yia[k][3] * yA[k][3]};
-          qA2131[k] = f2{-yia[k][2] * yA[k][2], -yia[k][3] * yA[k][4]};
-          qhd01[k] = f2{yhd[k][0], yhd[k][1]}, qhd23[k] = f2{yhd[k][2], yhd[k][3]};
-        }
+        sA10[k] = -yia[k][1] * yA[k][0], sA32[k] = -yia[k][3] * yA[k][5];
+        qA2030[k] = f2{-yia[k][2] * yA[k][1], -yia[k][3] * yA[k][3]};
+        qA2131[k] = f2{-yia[k][2] * yA[k][2], -yia[k][3] * yA[k][4]};
+        qhd01[k] = f2{yhd[k][0], yhd[k][1]}, qhd23[k] = f2{yhd[k][2], yhd[k][3]};
       }
-      if constexpr (QUAD && decltype(pk)::value) {
+      {
         // own contact (sub): mu, R, forces; its residuals from y; the folded coefficients
         const float muo = sub == 0 ? ymu[0] : sub == 1 ? ymu[1] : sub == 2 ? ymu[2] : ymu[3];
         const float Rpo = sub == 0 ? yRp[0] : sub == 1 ? yRp[1] : sub == 2 ? yRp[2] : yRp[3];
@@ -1476,14 +1386,13 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
           }
         }
       }
-    }
-  };
-  // One sweep over the block.  Per contact the 4 edges are a 4x4 Gauss-Seidel on the
-  // edge Gram matrix: every residual starts from the contact's y, and each force step
-  // adds A_ed df_d to the later edges' residuals, so the dependent chain per edge is
-  // mul -> max -> fma (df = max(-res/ARdiag, -f) is the projected step f' - f).
-  auto yblock_contact = [&](const int j, float& improvement, f2& impq, float (&dsel)[4], auto coupled, auto pk) {
-    if constexpr (QUAD && decltype(pk)::value) {  // packed residual form; contact j's residuals live in lane j
+    };
+    // One sweep over the block.  Per contact the 4 edges are a 4x4 Gauss-Seidel on the
+    // edge Gram matrix: every residual starts from the contact's y, and each force step
+    // adds A_ed df_d to the later edges' residuals, so the dependent chain per edge is
+    // mul -> max -> fma (df = max(-res/ARdiag, -f) is the projected step f' - f).
+    // Packed residual form: contact j's residuals live in lane j of the quad.
+    auto yblock_contact = [&](const int j, f2& impq, float (&dsel)[4], auto coupled) {
       const f2 c01 = f2{cfo[j][0], cfo[j][1]}, c23 = f2{cfo[j][2], cfo[j][3]};
       const f2 s01 = f2{qbcast(ro01.x, j), qbcast(ro01.y, j)};  // scaled residuals of contact j
       f2 s23 = f2{qbcast(ro23.x, j), qbcast(ro23.y, j)};
@@ -1513,102 +1422,31 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
 #pragma unroll                                   // contact's steps, the quad sums them before E
         for (int ed = 0; ed < 4; ed++) dsel[ed] = sub == j ? dfs[ed] : dsel[ed];
       }
-    } else if constexpr (NF == 1 && CON) {
-      {
-        float a, b, cc;
-        if constexpr (QUAD) {  // contact j's y lives in lane j of the quad
-          a = qbcast(yo[0], j), b = qbcast(yo[1], j), cc = qbcast(yo[2], j);
-        } else {
-          a = yb[j][0], b = yb[j][1], cc = yb[j][2];
-        }
-        const float mu = ymu[j], Rp = yRp[j];
-        float r[4], df[4];
-        r[0] = fmaf(Rp, cfo[j][0], fmaf(mu, b, a));
-        r[1] = fmaf(Rp, cfo[j][1], fmaf(-mu, b, a));
-        r[2] = fmaf(Rp, cfo[j][2], fmaf(mu, cc, a));
-        r[3] = fmaf(Rp, cfo[j][3], fmaf(-mu, cc, a));
-        int q = 0;
-#pragma unroll
-        for (int ed = 0; ed < 4; ed++) {
-#pragma unroll
-          for (int d = 0; d < ed; d++) r[ed] = fmaf(yA[j][q++], df[d], r[ed]);
-          df[ed] = fmaxf(r[ed] * -yia[j][ed], -cfo[j][ed]);
-        }
-#pragma unroll
-        for (int ed = 0; ed < 4; ed++) {
-          cfo[j][ed] += df[ed];
-          improvement = fmaf(-df[ed], fmaf(yhd[j][ed], df[ed], r[ed]), improvement);
-        }
-        const float D[3] = {(df[0] + df[1]) + (df[2] + df[3]), mu * (df[0] - df[1]), mu * (df[2] - df[3])};
-        if constexpr (QUAD) {  // this lane's contact moves by its row of the cross-Gram
-#pragma unroll
-          for (int rr = 0; rr < 3; rr++)
-            yo[rr] = fmaf(xr[j][3 * rr], D[0], fmaf(xr[j][3 * rr + 1], D[1], fmaf(xr[j][3 * rr + 2], D[2], yo[rr])));
-        }
-        if constexpr (!QUAD) {
-          const float* G = yG[j];
-          yb[j][0] = fmaf(G[0], D[0], fmaf(G[1], D[1], fmaf(G[2], D[2], a)));
-          yb[j][1] = fmaf(G[1], D[0], fmaf(G[3], D[1], fmaf(G[4], D[2], b)));
-          yb[j][2] = fmaf(G[2], D[0], fmaf(G[4], D[1], fmaf(G[5], D[2], cc)));
-        }
-#pragma unroll
-        for (int k = 0; k < FC; k++) {
-          if (QUAD || k == j) continue;
-#pragma unroll
-          for (int rr = 0; rr < 3; rr++) {
-            float s = yb[k][rr];
-#pragma unroll
-            for (int qq = 0; qq < 3; qq++)
-              s = fmaf(k < j ? xg[ypair(k, j)][3 * rr + qq] : xg[ypair(j, k)][3 * qq + rr], D[qq], s);
-            yb[k][rr] = s;
-          }
-        }
-        if constexpr (decltype(coupled)::value) {  // the extra contact shares the free body
-#pragma unroll
-          for (int q = 0; q < 3; q++) {
-            float s = yE[q];
-#pragma unroll
-            for (int rr = 0; rr < 3; rr++) s = fmaf(EX(E_X + 9 * j + 3 * rr + q), D[rr], s);
-            yE[q] = s;
-          }
-        }
-      }
-    }
-  };
-  // dof-frictionloss rows of the y variants, short-chain form: df = clamp(-res/ARdiag,
-  // -fl - f, fl - f) (the projected step), v_arm += M^-1 e_i df
-  auto fric_row_y = [&](const int i, float& improvement, auto ext, auto pk, float& famax) {
-    {
+    };
+    // dof-frictionloss rows of the y variants, short-chain form: df = clamp(-res/ARdiag,
+    // -fl - f, fl - f) (the projected step), v_arm += M^-1 e_i df
+    auto fric_row_y = [&](const int i, float& improvement, auto ext, float& famax) {
       const float fl = m.dof_frictionloss[i];
       const float res = fmaf(fR[i], ff[i], v[i] - fa[i]);
       const float fn = fminf(fmaxf(fmaf(res, -fiD[i], ff[i]), -fl), fl);
       const float df = fn - ff[i];
       famax += fabsf(df);  // a NaN step keeps famax from passing the retire test
-      if constexpr (decltype(pk)::value) {
 #pragma unroll
-        for (int k = 0; k + 1 < NA; k += 2) {  // v_arm += M^-1 e_i df, two dofs per packed FMA
-          const f2 t = fma2(Mp[i][k >> 1], splat2(df), f2{v[k], v[k + 1]});
-          v[k] = t.x, v[k + 1] = t.y;
-        }
-        if constexpr (NA & 1) v[NA - 1] = fmaf(Mi.a(i, NA - 1), df, v[NA - 1]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < NA; k++) v[k] = fmaf(Mi.a(i, k), df, v[k]);
+      for (int k = 0; k + 1 < NA; k += 2) {  // v_arm += M^-1 e_i df, two dofs per packed FMA
+        const f2 t = fma2(Mp[i][k >> 1], splat2(df), f2{v[k], v[k + 1]});
+        v[k] = t.x, v[k + 1] = t.y;
       }
+      if constexpr (NA & 1) v[NA - 1] = fmaf(Mi.a(i, NA - 1), df, v[NA - 1]);
       if constexpr (decltype(ext)::value) {  // the extra contact's y: J_E M^-1 e_i = W_E[i]
 #pragma unroll
         for (int q = 0; q < 3; q++)
-          yE[q] = fmaf(decltype(pk)::value ? ((i & 1) ? xq.eWp[3 * q + (i >> 1)].y : xq.eWp[3 * q + (i >> 1)].x)
-                                           : EX(E_W + 6 * q + i),
-                       df, yE[q]);
+          yE[q] = fmaf((i & 1) ? xq.eWp[3 * q + (i >> 1)].y : xq.eWp[3 * q + (i >> 1)].x, df, yE[q]);
       }
       ff[i] = fn;
       improvement = fmaf(-df, fmaf(fhD[i], df, res), improvement);
-    }
-  };
-  // after the sweeps: the free body's velocity from the block's force change
-  auto yblock_finish = [&]() {
-    if constexpr (NF == 1 && CON) {
+    };
+    // after the sweeps: the free body's velocity from the block's force change
+    auto yblock_finish = [&]() {
 #pragma unroll
       for (int k = 0; k < FC; k++) {
         const int c = cslot[k];
@@ -1623,26 +1461,24 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
                            fmaf(L.at(c, NA + i), Dn, fmaf(L.at(c, 12 + NA + i), D1, L.at(c, 24 + NA + i) * D2)),
                            v[NA + i]);
       }
-    }
-  };
-  // edge Gram off-diagonals A_ed (d < e) of a contact from its 3x3 Gram block and mu
-  auto edge_gram = [](const float G[6], float mu, float A[6]) {
-    auto gt = [&](int e) { return (e >> 1) ? G[2] : G[1]; };
-    auto gtt = [&](int e, int d) {
-      const int te = e >> 1, td = d >> 1;
-      return te == td ? (te ? G[5] : G[3]) : G[4];
     };
-    auto sg = [&](int e) { return (e & 1) ? -mu : mu; };
-    int q = 0;
+    // edge Gram off-diagonals A_ed (d < e) of a contact from its 3x3 Gram block and mu
+    auto edge_gram = [](const float G[6], float mu, float A[6]) {
+      auto gt = [&](int e) { return (e >> 1) ? G[2] : G[1]; };
+      auto gtt = [&](int e, int d) {
+        const int te = e >> 1, td = d >> 1;
+        return te == td ? (te ? G[5] : G[3]) : G[4];
+      };
+      auto sg = [&](int e) { return (e & 1) ? -mu : mu; };
+      int q = 0;
 #pragma unroll
-    for (int ed = 1; ed < 4; ed++)
+      for (int ed = 1; ed < 4; ed++)
 #pragma unroll
-      for (int d = 0; d < ed; d++) A[q++] = G[0] + sg(ed) * gt(ed) + sg(d) * gt(d) + sg(ed) * sg(d) * gtt(ed, d);
-  };
-  // Set up E (record cE) and F (record cF); an absent slot is the zero record: 1/ARdiag = 0
-  // and f = 0, so its steps are exact no-ops.
-  auto yext_setup = [&](int cE, int cF) {
-    if constexpr (NF == 1 && CON) {
+        for (int d = 0; d < ed; d++) A[q++] = G[0] + sg(ed) * gt(ed) + sg(d) * gt(d) + sg(ed) * sg(d) * gtt(ed, d);
+    };
+    // Set up E (record cE) and F (record cF); an absent slot is the zero record: 1/ARdiag = 0
+    // and f = 0, so its steps are exact no-ops.
+    auto yext_setup = [&](int cE, int cF) {
       // ---- E: W_E, y_E, cross-Gram with the block, chain constants
 #pragma unroll
       for (int q = 0; q < 3; q++) {
@@ -1739,225 +1575,135 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
 #pragma unroll
         for (int i = 0; i < 6; i++) EX(F_A + i) = A[i];
       }
-    }
-  };
-  // one sweep step of F (arm-only, before E in row order): v-form on the arm (its y from
-  // three NA-dof dots), the edge chain, v_arm += W_F D, and E's y by X_EF D
-  auto yf_row = [&](float& improvement) {
-    if constexpr (NF == 1 && CON) {
-      const float mu = EX(F_MUX), Rp = EX(F_RPX);
-      float y[3];
+    };
+    // quad mode, packed: the block's accumulated steps on y_E (lane-split X_kE D_k)
+    auto yblock_to_e = [&](const float (&dsel)[4]) {
+      const float mu = xq.muo;
+      const float D[3] = {(dsel[0] + dsel[1]) + (dsel[2] + dsel[3]), mu * (dsel[0] - dsel[1]), mu * (dsel[2] - dsel[3])};
 #pragma unroll
       for (int q = 0; q < 3; q++) {
-        float t = -EX(F_SH + q);
+        float p = 0.f;
 #pragma unroll
-        for (int i = 0; i < NA; i++) t = fmaf(EX(F_J + 6 * q + i), v[i], t);
-        y[q] = t;
+        for (int rr = 0; rr < 3; rr++) p = fmaf(xq.xo[3 * rr + q], D[rr], p);
+        yE[q] += qsum(p);
       }
-      float r[4], df[4];
-      r[0] = fmaf(Rp, fF[0], fmaf(mu, y[1], y[0]));
-      r[1] = fmaf(Rp, fF[1], fmaf(-mu, y[1], y[0]));
-      r[2] = fmaf(Rp, fF[2], fmaf(mu, y[2], y[0]));
-      r[3] = fmaf(Rp, fF[3], fmaf(-mu, y[2], y[0]));
-      int q = 0;
-#pragma unroll
-      for (int ed = 0; ed < 4; ed++) {
-#pragma unroll
-        for (int d = 0; d < ed; d++) r[ed] = fmaf(EX(F_A + q++), df[d], r[ed]);
-        df[ed] = fmaxf(r[ed] * -EX(F_IA + ed), -fF[ed]);
-      }
-#pragma unroll
-      for (int ed = 0; ed < 4; ed++) {
-        fF[ed] += df[ed];
-        improvement = fmaf(-df[ed], fmaf(EX(F_HD + ed), df[ed], r[ed]), improvement);
-      }
-      const float D[3] = {(df[0] + df[1]) + (df[2] + df[3]), mu * (df[0] - df[1]), mu * (df[2] - df[3])};
-#pragma unroll
-      for (int i = 0; i < NA; i++)
-        v[i] = fmaf(EX(F_W + i), D[0], fmaf(EX(F_W + 6 + i), D[1], fmaf(EX(F_W + 12 + i), D[2], v[i])));
-#pragma unroll
-      for (int qq = 0; qq < 3; qq++)
-        yE[qq] = fmaf(EX(F_XE + 3 * qq), D[0], fmaf(EX(F_XE + 3 * qq + 1), D[1], fmaf(EX(F_XE + 3 * qq + 2), D[2], yE[qq])));
-    }
-  };
-  // quad mode, packed: the block's accumulated steps on y_E (lane-split X_kE D_k)
-  auto yblock_to_e = [&](const float (&dsel)[4]) {
-    const float mu = xq.muo;
-    const float D[3] = {(dsel[0] + dsel[1]) + (dsel[2] + dsel[3]), mu * (dsel[0] - dsel[1]), mu * (dsel[2] - dsel[3])};
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-      float p = 0.f;
-#pragma unroll
-      for (int rr = 0; rr < 3; rr++) p = fmaf(xq.xo[3 * rr + q], D[rr], p);
-      yE[q] += qsum(p);
-    }
-  };
-  // quad mode, packed: one edge chain (pyramid of 4 edges) from y = (a, b, c)
-  // scaled residuals as in the block (s = -r / ARdiag; nia = -1/ARdiag per edge, the A's
-  // pre-scaled by the -1/ARdiag of the edge they move), steps built in their pairs
-  auto qchain = [&](float a, float b, float c, float (&f)[4], float mu, float Rp, f2 nia01, f2 nia23, float A10,
-                    f2 A2030, f2 A2131, float A32, f2 hd01, f2 hd23, f2& imp, float (&df)[4]) {
-    const f2 c01 = f2{f[0], f[1]}, c23 = f2{f[2], f[3]};
-    const f2 s01 = fma2(splat2(Rp), c01, fma2(f2{mu, -mu}, splat2(b), splat2(a))) * nia01;
-    f2 s23 = fma2(splat2(Rp), c23, fma2(f2{mu, -mu}, splat2(c), splat2(a))) * nia23;
-    f2 d01, d23;
-    d01.x = max_neg(s01.x, c01.x);
-    const float s1 = fmaf(A10, d01.x, s01.y);
-    s23 = fma2(A2030, d01.xx, s23);
-    d01.y = max_neg(s1, c01.y);
-    s23 = fma2_hi(A2131, d01, s23);
-    d23.x = max_neg(s23.x, c23.x);
-    const float s3 = fmaf(A32, d23.x, s23.y);
-    d23.y = max_neg(s3, c23.y);
-    df[0] = d01.x, df[1] = d01.y, df[2] = d23.x, df[3] = d23.y;
-    const f2 n01 = c01 + d01, n23 = c23 + d23;
-    f[0] = n01.x, f[1] = n01.y, f[2] = n23.x, f[3] = n23.y;
-    imp = fma2(-(hd01 * d01), fma2(f2{s01.x, s1}, splat2(-2.f), d01), imp);
-    imp = fma2(-(hd23 * d23), fma2(f2{s23.x, s3}, splat2(-2.f), d23), imp);
-  };
-  // v_arm += W D with W as dof pairs (W[q] row pairs)
-  auto qvarm = [&](const f2 (&Wp)[9], const float (&D)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      f2 t = f2{v[2 * k], v[2 * k + 1]};
-#pragma unroll
-      for (int q = 0; q < 3; q++) t = fma2(Wp[3 * q + k], splat2(D[q]), t);
-      v[2 * k] = t.x, v[2 * k + 1] = t.y;
-    }
-  };
-  auto yf_row_q = [&](f2& imp, float& famax) {
-    f2 y01 = xq.fSh01;
-    float y2 = xq.fSh2;
-#pragma unroll
-    for (int i = 0; i < NA; i++) y01 = fma2(xq.fJp[i], splat2(v[i]), y01), y2 = fmaf(xq.fJ2[i], v[i], y2);
-    float df[4];
-    qchain(y01.x, y01.y, y2, fF, xq.fMu, xq.fRp, xq.fNia01, xq.fNia23, xq.fA10, xq.fA2030, xq.fA2131, xq.fA32, xq.fHD01, xq.fHD23,
-           imp, df);
-    famax += (fabsf(df[0]) + fabsf(df[1])) + (fabsf(df[2]) + fabsf(df[3]));
-    const float mu = xq.fMu;
-    const float D[3] = {(df[0] + df[1]) + (df[2] + df[3]), mu * (df[0] - df[1]), mu * (df[2] - df[3])};
-    qvarm(xq.fWp, D);
-    f2 e01 = f2{yE[0], yE[1]};
-#pragma unroll
-    for (int rr = 0; rr < 3; rr++) e01 = fma2(xq.fXp[rr], splat2(D[rr]), e01), yE[2] = fmaf(xq.fX2[rr], D[rr], yE[2]);
-    yE[0] = e01.x, yE[1] = e01.y;
-  };
-  // varm = false: v_arm is not read again during these sweeps (frictionloss rows retired, no F
-  // slot), so E's v_arm update is deferred to one product with its total force change
-  auto yext_row_q = [&](f2& imp, auto coupled, float& famax, auto varm) {
-    float df[4];
-    qchain(yE[0], yE[1], yE[2], fE, xq.eMu, xq.eRp, xq.eNia01, xq.eNia23, xq.eA10, xq.eA2030, xq.eA2131, xq.eA32, xq.eHD01, xq.eHD23,
-           imp, df);
-    if constexpr (!decltype(coupled)::value) famax += (fabsf(df[0]) + fabsf(df[1])) + (fabsf(df[2]) + fabsf(df[3]));
-    const float mu = xq.eMu;
-    const float D[3] = {(df[0] + df[1]) + (df[2] + df[3]), mu * (df[0] - df[1]), mu * (df[2] - df[3])};
-    if constexpr (decltype(varm)::value) qvarm(xq.eWp, D);
-    if constexpr (decltype(coupled)::value) {  // this lane's block contact moves by X_own,E D
-#pragma unroll
-      for (int qq = 0; qq < 3; qq++) {
-        ro01 = fma2(xq.qe01[qq], splat2(D[qq]), ro01);
-        ro23 = fma2(xq.qe23[qq], splat2(D[qq]), ro23);
-      }
-    }
-    f2 e01 = f2{yE[0], yE[1]};
-    float e2 = yE[2];
-#pragma unroll
-    for (int qq = 0; qq < 3; qq++) e01 = fma2(xq.eGp[qq], splat2(D[qq]), e01), e2 = fmaf(xq.eG2[qq], D[qq], e2);
-    yE[0] = e01.x, yE[1] = e01.y, yE[2] = e2;
-  };
-  // quad mode: preload the E/F coefficients (after yext_setup wrote them to LDS)
-  auto yext_preload = [&]() {
-#pragma unroll
-    for (int q = 0; q < 3; q++)
+    };
+    // quad mode, packed: one edge chain (pyramid of 4 edges) from y = (a, b, c)
+    // scaled residuals as in the block (s = -r / ARdiag; nia = -1/ARdiag per edge, the A's
+    // pre-scaled by the -1/ARdiag of the edge they move), steps built in their pairs
+    auto qchain = [&](float a, float b, float c, float (&f)[4], float mu, float Rp, f2 nia01, f2 nia23, float A10,
+                      f2 A2030, f2 A2131, float A32, f2 hd01, f2 hd23, f2& imp, float (&df)[4]) {
+      const f2 c01 = f2{f[0], f[1]}, c23 = f2{f[2], f[3]};
+      const f2 s01 = fma2(splat2(Rp), c01, fma2(f2{mu, -mu}, splat2(b), splat2(a))) * nia01;
+      f2 s23 = fma2(splat2(Rp), c23, fma2(f2{mu, -mu}, splat2(c), splat2(a))) * nia23;
+      f2 d01, d23;
+      d01.x = max_neg(s01.x, c01.x);
+      const float s1 = fmaf(A10, d01.x, s01.y);
+      s23 = fma2(A2030, d01.xx, s23);
+      d01.y = max_neg(s1, c01.y);
+      s23 = fma2_hi(A2131, d01, s23);
+      d23.x = max_neg(s23.x, c23.x);
+      const float s3 = fmaf(A32, d23.x, s23.y);
+      d23.y = max_neg(s3, c23.y);
+      df[0] = d01.x, df[1] = d01.y, df[2] = d23.x, df[3] = d23.y;
+      const f2 n01 = c01 + d01, n23 = c23 + d23;
+      f[0] = n01.x, f[1] = n01.y, f[2] = n23.x, f[3] = n23.y;
+      imp = fma2(-(hd01 * d01), fma2(f2{s01.x, s1}, splat2(-2.f), d01), imp);
+      imp = fma2(-(hd23 * d23), fma2(f2{s23.x, s3}, splat2(-2.f), d23), imp);
+    };
+    // v_arm += W D with W as dof pairs (W[q] row pairs)
+    auto qvarm = [&](const f2 (&Wp)[9], const float (&D)[3]) {
 #pragma unroll
       for (int k = 0; k < 3; k++) {
-        xq.eWp[3 * q + k] = f2{EX(E_W + 6 * q + 2 * k), EX(E_W + 6 * q + 2 * k + 1)};
-        xq.fWp[3 * q + k] = f2{EX(F_W + 6 * q + 2 * k), EX(F_W + 6 * q + 2 * k + 1)};
+        f2 t = f2{v[2 * k], v[2 * k + 1]};
+#pragma unroll
+        for (int q = 0; q < 3; q++) t = fma2(Wp[3 * q + k], splat2(D[q]), t);
+        v[2 * k] = t.x, v[2 * k + 1] = t.y;
       }
-    float eia[4], fia[4];  // -1/ARdiag of the E and F edges
+    };
+    // one sweep step of F (arm-only, before E in row order): v-form on the arm (its y from
+    // three NA-dof dots), the edge chain, v_arm += W_F D, and E's y by X_EF D
+    auto yf_row_q = [&](f2& imp, float& famax) {
+      f2 y01 = xq.fSh01;
+      float y2 = xq.fSh2;
 #pragma unroll
-    for (int ed = 0; ed < 4; ed++) eia[ed] = -EX(E_IA + ed), fia[ed] = -EX(F_IA + ed);
-    xq.eNia01 = f2{eia[0], eia[1]}, xq.eNia23 = f2{eia[2], eia[3]};
-    xq.fNia01 = f2{fia[0], fia[1]}, xq.fNia23 = f2{fia[2], fia[3]};
-    xq.eA10 = eia[1] * EX(E_A + 0), xq.eA32 = eia[3] * EX(E_A + 5);
-    xq.eA2030 = f2{eia[2] * EX(E_A + 1), eia[3] * EX(E_A + 3)}, xq.eA2131 = f2{eia[2] * EX(E_A + 2), eia[3] * EX(E_A + 4)};
-    xq.fA10 = fia[1] * EX(F_A + 0), xq.fA32 = fia[3] * EX(F_A + 5);
-    xq.fA2030 = f2{fia[2] * EX(F_A + 1), fia[3] * EX(F_A + 3)}, xq.fA2131 = f2{fia[2] * EX(F_A + 2), fia[3] * EX(F_A + 4)};
-    xq.eHD01 = f2{EX(E_HD + 0), EX(E_HD + 1)}, xq.eHD23 = f2{EX(E_HD + 2), EX(E_HD + 3)};
-    xq.fHD01 = f2{EX(F_HD + 0), EX(F_HD + 1)}, xq.fHD23 = f2{EX(F_HD + 2), EX(F_HD + 3)};
-    xq.eMu = EX(E_MU), xq.eRp = EX(E_RP), xq.fMu = EX(F_MUX), xq.fRp = EX(F_RPX);
-#pragma unroll
-    for (int i = 0; i < NA; i++) xq.fJp[i] = f2{EX(F_J + i), EX(F_J + 6 + i)}, xq.fJ2[i] = EX(F_J + 12 + i);
-#pragma unroll
-    for (int rr = 0; rr < 3; rr++) xq.fXp[rr] = f2{EX(F_XE + rr), EX(F_XE + 3 + rr)}, xq.fX2[rr] = EX(F_XE + 6 + rr);
-    xq.eGp[0] = f2{EX(E_G + 0), EX(E_G + 1)}, xq.eGp[1] = f2{EX(E_G + 1), EX(E_G + 3)}, xq.eGp[2] = f2{EX(E_G + 2), EX(E_G + 4)};
-    xq.eG2[0] = EX(E_G + 2), xq.eG2[1] = EX(E_G + 4), xq.eG2[2] = EX(E_G + 5);
-#pragma unroll
-    for (int t = 0; t < 9; t++) xq.xo[t] = EX(E_X + 9 * sub + t);
-    xq.muo = sub == 0 ? ymu[0] : sub == 1 ? ymu[1] : sub == 2 ? ymu[2] : ymu[3];
-#pragma unroll
-    for (int qq = 0; qq < 3; qq++) {  // residual form of X_own,E: rows (1, s_e on t(e)) of the own
-                                      // contact, scaled by its -1/ARdiag as the residuals are
-      xq.qe01[qq] = f2{fmaf(xq.muo, xq.xo[3 + qq], xq.xo[qq]), fmaf(-xq.muo, xq.xo[3 + qq], xq.xo[qq])} * own_nia01();
-      xq.qe23[qq] = f2{fmaf(xq.muo, xq.xo[6 + qq], xq.xo[qq]), fmaf(-xq.muo, xq.xo[6 + qq], xq.xo[qq])} * own_nia23();
-    }
-    xq.fSh01 = f2{-EX(F_SH + 0), -EX(F_SH + 1)}, xq.fSh2 = -EX(F_SH + 2);
-  };
-  // one sweep step of the extra contact (after the friction rows and the block)
-  auto yext_row = [&](float& improvement, auto coupled) {
-    if constexpr (NF == 1 && CON) {
-      const float mu = EX(E_MU), Rp = EX(E_RP);
-      float r[4], df[4];
-      r[0] = fmaf(Rp, fE[0], fmaf(mu, yE[1], yE[0]));
-      r[1] = fmaf(Rp, fE[1], fmaf(-mu, yE[1], yE[0]));
-      r[2] = fmaf(Rp, fE[2], fmaf(mu, yE[2], yE[0]));
-      r[3] = fmaf(Rp, fE[3], fmaf(-mu, yE[2], yE[0]));
-      int q = 0;
-#pragma unroll
-      for (int ed = 0; ed < 4; ed++) {
-#pragma unroll
-        for (int d = 0; d < ed; d++) r[ed] = fmaf(EX(E_A + q++), df[d], r[ed]);
-        df[ed] = fmaxf(r[ed] * -EX(E_IA + ed), -fE[ed]);
-      }
-#pragma unroll
-      for (int ed = 0; ed < 4; ed++) {
-        fE[ed] += df[ed];
-        improvement = fmaf(-df[ed], fmaf(EX(E_HD + ed), df[ed], r[ed]), improvement);
-      }
+      for (int i = 0; i < NA; i++) y01 = fma2(xq.fJp[i], splat2(v[i]), y01), y2 = fmaf(xq.fJ2[i], v[i], y2);
+      float df[4];
+      qchain(y01.x, y01.y, y2, fF, xq.fMu, xq.fRp, xq.fNia01, xq.fNia23, xq.fA10, xq.fA2030, xq.fA2131, xq.fA32, xq.fHD01, xq.fHD23,
+             imp, df);
+      famax += (fabsf(df[0]) + fabsf(df[1])) + (fabsf(df[2]) + fabsf(df[3]));
+      const float mu = xq.fMu;
       const float D[3] = {(df[0] + df[1]) + (df[2] + df[3]), mu * (df[0] - df[1]), mu * (df[2] - df[3])};
+      qvarm(xq.fWp, D);
+      f2 e01 = f2{yE[0], yE[1]};
 #pragma unroll
-      for (int i = 0; i < NA; i++)
-        v[i] = fmaf(EX(E_W + i), D[0], fmaf(EX(E_W + 6 + i), D[1], fmaf(EX(E_W + 12 + i), D[2], v[i])));
-      if constexpr (decltype(coupled)::value) {
-        if constexpr (QUAD) {
+      for (int rr = 0; rr < 3; rr++) e01 = fma2(xq.fXp[rr], splat2(D[rr]), e01), yE[2] = fmaf(xq.fX2[rr], D[rr], yE[2]);
+      yE[0] = e01.x, yE[1] = e01.y;
+    };
+    // one sweep step of the extra contact (after the friction rows and the block)
+    // varm = false: v_arm is not read again during these sweeps (frictionloss rows retired, no F
+    // slot), so E's v_arm update is deferred to one product with its total force change
+    auto yext_row_q = [&](f2& imp, auto coupled, float& famax, auto varm) {
+      float df[4];
+      qchain(yE[0], yE[1], yE[2], fE, xq.eMu, xq.eRp, xq.eNia01, xq.eNia23, xq.eA10, xq.eA2030, xq.eA2131, xq.eA32, xq.eHD01, xq.eHD23,
+             imp, df);
+      if constexpr (!decltype(coupled)::value) famax += (fabsf(df[0]) + fabsf(df[1])) + (fabsf(df[2]) + fabsf(df[3]));
+      const float mu = xq.eMu;
+      const float D[3] = {(df[0] + df[1]) + (df[2] + df[3]), mu * (df[0] - df[1]), mu * (df[2] - df[3])};
+      if constexpr (decltype(varm)::value) qvarm(xq.eWp, D);
+      if constexpr (decltype(coupled)::value) {  // this lane's block contact moves by X_own,E D
 #pragma unroll
-          for (int rr = 0; rr < 3; rr++) {
-            float s = yo[rr];
-#pragma unroll
-            for (int qq = 0; qq < 3; qq++) s = fmaf(EX(E_X + 9 * sub + 3 * rr + qq), D[qq], s);
-            yo[rr] = s;
-          }
-        } else {
-#pragma unroll
-          for (int k = 0; k < FC; k++)
-#pragma unroll
-            for (int rr = 0; rr < 3; rr++) {
-              float s = yb[k][rr];
-#pragma unroll
-              for (int qq = 0; qq < 3; qq++) s = fmaf(EX(E_X + 9 * k + 3 * rr + qq), D[qq], s);
-              yb[k][rr] = s;
-            }
+        for (int qq = 0; qq < 3; qq++) {
+          ro01 = fma2(xq.qe01[qq], splat2(D[qq]), ro01);
+          ro23 = fma2(xq.qe23[qq], splat2(D[qq]), ro23);
         }
       }
-      const float y0 = yE[0], y1 = yE[1], y2 = yE[2];
-      yE[0] = fmaf(EX(E_G + 0), D[0], fmaf(EX(E_G + 1), D[1], fmaf(EX(E_G + 2), D[2], y0)));
-      yE[1] = fmaf(EX(E_G + 1), D[0], fmaf(EX(E_G + 3), D[1], fmaf(EX(E_G + 4), D[2], y1)));
-      yE[2] = fmaf(EX(E_G + 2), D[0], fmaf(EX(E_G + 4), D[1], fmaf(EX(E_G + 5), D[2], y2)));
-    }
-  };
-  // after the sweeps: E's forces back to its record; its free-body part moves v6
-  auto yext_finish = [&](int c, bool hasE, int cF, bool hasF, auto coupled) {
-    if constexpr (NF == 1 && CON) {
+      f2 e01 = f2{yE[0], yE[1]};
+      float e2 = yE[2];
+#pragma unroll
+      for (int qq = 0; qq < 3; qq++) e01 = fma2(xq.eGp[qq], splat2(D[qq]), e01), e2 = fmaf(xq.eG2[qq], D[qq], e2);
+      yE[0] = e01.x, yE[1] = e01.y, yE[2] = e2;
+    };
+    // quad mode: preload the E/F coefficients (after yext_setup wrote them to LDS)
+    auto yext_preload = [&]() {
+#pragma unroll
+      for (int q = 0; q < 3; q++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          xq.eWp[3 * q + k] = f2{EX(E_W + 6 * q + 2 * k), EX(E_W + 6 * q + 2 * k + 1)};
+          xq.fWp[3 * q + k] = f2{EX(F_W + 6 * q + 2 * k), EX(F_W + 6 * q + 2 * k + 1)};
+        }
+      float eia[4], fia[4];  // -1/ARdiag of the E and F edges
+#pragma unroll
+      for (int ed = 0; ed < 4; ed++) eia[ed] = -EX(E_IA + ed), fia[ed] = -EX(F_IA + ed);
+      xq.eNia01 = f2{eia[0], eia[1]}, xq.eNia23 = f2{eia[2], eia[3]};
+      xq.fNia01 = f2{fia[0], fia[1]}, xq.fNia23 = f2{fia[2], fia[3]};
+      xq.eA10 = eia[1] * EX(E_A + 0), xq.eA32 = eia[3] * EX(E_A + 5);
+      xq.eA2030 = f2{eia[2] * EX(E_A + 1), eia[3] * EX(E_A + 3)}, xq.eA2131 = f2{eia[2] * EX(E_A + 2), eia[3] * EX(E_A + 4)};
+      xq.fA10 = fia[1] * EX(F_A + 0), xq.fA32 = fia[3] * EX(F_A + 5);
+      xq.fA2030 = f2{fia[2] * EX(F_A + 1), fia[3] * EX(F_A + 3)}, xq.fA2131 = f2{fia[2] * EX(F_A + 2), fia[3] * EX(F_A + 4)};
+      xq.eHD01 = f2{EX(E_HD + 0), EX(E_HD + 1)}, xq.eHD23 = f2{EX(E_HD + 2), EX(E_HD + 3)};
+      xq.fHD01 = f2{EX(F_HD + 0), EX(F_HD + 1)}, xq.fHD23 = f2{EX(F_HD + 2), EX(F_HD + 3)};
+      xq.eMu = EX(E_MU), xq.eRp = EX(E_RP), xq.fMu = EX(F_MUX), xq.fRp = EX(F_RPX);
+#pragma unroll
+      for (int i = 0; i < NA; i++) xq.fJp[i] = f2{EX(F_J + i), EX(F_J + 6 + i)}, xq.fJ2[i] = EX(F_J + 12 + i);
+#pragma unroll
+      for (int rr = 0; rr < 3; rr++) xq.fXp[rr] = f2{EX(F_XE + rr), EX(F_XE + 3 + rr)}, xq.fX2[rr] = EX(F_XE + 6 + rr);
+      xq.eGp[0] = f2{EX(E_G + 0), EX(E_G + 1)}, xq.eGp[1] = f2{EX(E_G + 1), EX(E_G + 3)}, xq.eGp[2] = f2{EX(E_G + 2), EX(E_G + 4)};
+      xq.eG2[0] = EX(E_G + 2), xq.eG2[1] = EX(E_G + 4), xq.eG2[2] = EX(E_G + 5);
+#pragma unroll
+      for (int t = 0; t < 9; t++) xq.xo[t] = EX(E_X + 9 * sub + t);
+      xq.muo = sub == 0 ? ymu[0] : sub == 1 ? ymu[1] : sub == 2 ? ymu[2] : ymu[3];
+#pragma unroll
+      for (int qq = 0; qq < 3; qq++) {  // residual form of X_own,E: rows (1, s_e on t(e)) of the own
+                                        // contact, scaled by its -1/ARdiag as the residuals are
+        xq.qe01[qq] = f2{fmaf(xq.muo, xq.xo[3 + qq], xq.xo[qq]), fmaf(-xq.muo, xq.xo[3 + qq], xq.xo[qq])} * own_nia01();
+        xq.qe23[qq] = f2{fmaf(xq.muo, xq.xo[6 + qq], xq.xo[qq]), fmaf(-xq.muo, xq.xo[6 + qq], xq.xo[qq])} * own_nia23();
+      }
+      xq.fSh01 = f2{-EX(F_SH + 0), -EX(F_SH + 1)}, xq.fSh2 = -EX(F_SH + 2);
+    };
+    // after the sweeps: E's forces back to its record; its free-body part moves v6
+    auto yext_finish = [&](int c, bool hasE, int cF, bool hasF, auto coupled) {
       if (hasF) {
 #pragma unroll
         for (int ed = 0; ed < 4; ed++) L.at(cF, F_FRC + ed) = fF[ed];
@@ -1978,154 +1724,135 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
 #pragma unroll
         for (int ed = 0; ed < 4; ed++) L.at(c, F_FRC + ed) = fE[ed];
       }
-    }
-  };
-  // extras in row order: F = the first of two (arm-only), E = the last one
-  const int cE = npost >= 1 ? xidx(npost - 1) : LDS_CON, cF = npost == 2 ? xidx(0) : LDS_CON;
-  const bool hasE = npost >= 1, hasF = npost == 2;
-  auto ysweeps = [&](auto ext, auto coupled, auto ext2) {
-    yblock_setup();
-    using PK = std::integral_constant<bool, QUAD>;
-    yblock_consts(PK{});
-    if constexpr (PK::value) {
+    };
+    // extras in row order: F = the first of two (arm-only), E = the last one
+    const int cE = npost >= 1 ? xidx(npost - 1) : LDS_CON, cF = npost == 2 ? xidx(0) : LDS_CON;
+    const bool hasE = npost >= 1, hasF = npost == 2;
+    auto ysweeps = [&](auto ext, auto coupled, auto ext2) {
+      yblock_setup();
+      yblock_consts();
 #pragma unroll
       for (int i = 0; i < NA; i++)
 #pragma unroll
         for (int k = 0; k + 1 < NA; k += 2) Mp[i][k >> 1] = f2{Mi.a(i, k), Mi.a(i, k + 1)};
-    }
-    if constexpr (decltype(ext)::value) {
-      yext_setup(cE, cF);
-      if constexpr (PK::value) yext_preload();
-    }
-    // one sweep; ARM = false leaves out the arm's rows, FRIC = false only its frictionloss
-    // rows (see below).  Returns the improvement; famax gets the sum of |df| over the arm's
-    // rows (ffmax: over its frictionloss rows).
-    auto sweep = [&](auto arm, auto fric, float& famax, float& ffmax) {
-      // the arm's frictionloss rows and the cube block touch disjoint dofs (M is block
-      // diagonal): the two Gauss-Seidel chains commute, so their rows are interleaved in
-      // program order to give the (latency-bound) issue stream independent work; the
-      // improvement terms go to one accumulator per chain
-      float improvement = 0.f, imp_b = 0.f;
-      f2 impq = f2{0.f, 0.f};
-      float dsel[4] = {0.f, 0.f, 0.f, 0.f};
-      // (NA = 6, FC = 4: rows {0,1} c0 {2} c1 {3,4} c2 {5} c3)
+      if constexpr (decltype(ext)::value) {
+        yext_setup(cE, cF);
+        yext_preload();
+      }
+      // one sweep; ARM = false leaves out the arm's rows, FRIC = false only its frictionloss
+      // rows (see below).  Returns the improvement; famax gets the sum of |df| over the arm's
+      // rows (ffmax: over its frictionloss rows).
+      auto sweep = [&](auto arm, auto fric, float& famax, float& ffmax) {
+        // the arm's frictionloss rows and the cube block touch disjoint dofs (M is block
+        // diagonal): the two Gauss-Seidel chains commute, so their rows are interleaved in
+        // program order to give the (latency-bound) issue stream independent work; the
+        // improvement terms go to one accumulator per chain
+        float improvement = 0.f;
+        f2 impq = f2{0.f, 0.f};
+        float dsel[4] = {0.f, 0.f, 0.f, 0.f};
+        // (NA = 6, FC = 4: rows {0,1} c0 {2} c1 {3,4} c2 {5} c3)
 #pragma unroll
-      for (int j = 0; j < FC; j++) {
-        if constexpr (decltype(arm)::value && decltype(fric)::value) {
+        for (int j = 0; j < FC; j++) {
+          if constexpr (decltype(arm)::value && decltype(fric)::value) {
 #pragma unroll
-          for (int i = (j * NA + FC - 1) / FC; i < ((j + 1) * NA + FC - 1) / FC; i++)
-            fric_row_y(i, improvement, ext, PK{}, ffmax);
+            for (int i = (j * NA + FC - 1) / FC; i < ((j + 1) * NA + FC - 1) / FC; i++)
+              fric_row_y(i, improvement, ext, ffmax);
+          }
+          yblock_contact(j, impq, dsel, coupled);
         }
-        yblock_contact(j, imp_b, impq, dsel, coupled, PK{});
-      }
-      if constexpr (FC == 0) {
-#pragma unroll
-        for (int i = 0; i < NA; i++) fric_row_y(i, improvement, ext, PK{}, ffmax);
-      }
-      if constexpr (PK::value) {
         if constexpr (decltype(ext)::value && decltype(coupled)::value) yblock_to_e(dsel);
         if constexpr (decltype(arm)::value && decltype(ext2)::value) yf_row_q(impq, famax);
         if constexpr (decltype(arm)::value && decltype(ext)::value)
           yext_row_q(impq, coupled, famax, std::integral_constant<bool, decltype(fric)::value || decltype(ext2)::value>{});
         improvement += impq.x + impq.y;
-      } else {
-        improvement += imp_b;
-        if constexpr (decltype(ext2)::value) yf_row(improvement);
-        if constexpr (decltype(ext)::value) yext_row(improvement, coupled);
-      }
-      return improvement;
-    };
-    // Arm retirement.  Unless an extra contact touches the cube, the arm's rows (its dof
-    // frictionloss rows and the arm-only extra slots E/F) and the cube block share no dof:
-    // two Gauss-Seidel systems that only meet in the stopping test.  Once a sweep moves the
-    // arm's forces by at most ARM_RETIRE in total (N, N m) on every lane of the wave, the
-    // remaining sweeps run the block alone (the pure block converges ~95 sweeps slower than
-    // the arm, which settles in ~3).  The threshold sits an order below what MuJoCo's own
-    // stopping test resolves: a row's step df lowers the cost by >= ARdiag df^2 / 2, and the
-    // solve stops at improvement / trace(M) < tolerance (1e-8), which for the arm's rows
-    // (ARdiag ~ 30, trace(M) ~ 0.3) leaves steps of order 1e-5.  Exactly-zero steps (the
-    // common case: frictionloss rows saturated at +-frictionloss) leave the result bit for
-    // bit equal to sweeping all rows.
-    constexpr bool RETIRE = PK::value && FC > 0 && !decltype(coupled)::value;
-    // Frictionloss retirement (the extra-slot variants).  The arm's 6 frictionloss rows settle
-    // within a few sweeps (saturated at +-frictionloss, or holding), while an extra contact E
-    // (arm on the table, or the gripper on the cube) keeps its Gauss-Seidel chain going for
-    // tens of sweeps -- all ~95 of them when it touches the cube, which rules out the arm
-    // retirement above.  Once one sweep moves the frictionloss forces by at most ARM_RETIRE in
-    // total on every lane, the remaining sweeps leave those rows out and run E (and F) with
-    // the block: the same threshold argument as the arm retirement, applied to the rows that
-    // have settled.
-    constexpr bool FRETIRE = PK::value && FC > 0 && decltype(ext)::value;
-    int it = 0;
-    bool done = false, fret = false;
-    for (; it < m.iterations; it++) {
-      float famax = 0.f, ffmax = 0.f;
-      if (sweep(std::true_type{}, std::true_type{}, famax, ffmax) * scale < m.tolerance) {
-        done = true;
-        break;
-      }
-      if constexpr (RETIRE) {
-        if (__all(famax + ffmax <= ARM_RETIRE)) {
-#ifdef SOARM_PHASE_PROF
-          armstop = it + 1;
-#endif
-          it++;
+        return improvement;
+      };
+      // Arm retirement.  Unless an extra contact touches the cube, the arm's rows (its dof
+      // frictionloss rows and the arm-only extra slots E/F) and the cube block share no dof:
+      // two Gauss-Seidel systems that only meet in the stopping test.  Once a sweep moves the
+      // arm's forces by at most ARM_RETIRE in total (N, N m) on every lane of the wave, the
+      // remaining sweeps run the block alone (the pure block converges ~95 sweeps slower than
+      // the arm, which settles in ~3).  The threshold sits an order below what MuJoCo's own
+      // stopping test resolves: a row's step df lowers the cost by >= ARdiag df^2 / 2, and the
+      // solve stops at improvement / trace(M) < tolerance (1e-8), which for the arm's rows
+      // (ARdiag ~ 30, trace(M) ~ 0.3) leaves steps of order 1e-5.  Exactly-zero steps (the
+      // common case: frictionloss rows saturated at +-frictionloss) leave the result bit for
+      // bit equal to sweeping all rows.
+      constexpr bool RETIRE = !decltype(coupled)::value;
+      // Frictionloss retirement (the extra-slot variants).  The arm's 6 frictionloss rows settle
+      // within a few sweeps (saturated at +-frictionloss, or holding), while an extra contact E
+      // (arm on the table, or the gripper on the cube) keeps its Gauss-Seidel chain going for
+      // tens of sweeps -- all ~95 of them when it touches the cube, which rules out the arm
+      // retirement above.  Once one sweep moves the frictionloss forces by at most ARM_RETIRE in
+      // total on every lane, the remaining sweeps leave those rows out and run E (and F) with
+      // the block: the same threshold argument as the arm retirement, applied to the rows that
+      // have settled.
+      constexpr bool FRETIRE = decltype(ext)::value;
+      int it = 0;
+      bool done = false, fret = false;
+      for (; it < m.iterations; it++) {
+        float famax = 0.f, ffmax = 0.f;
+        if (sweep(std::true_type{}, std::true_type{}, famax, ffmax) * scale < m.tolerance) {
+          done = true;
           break;
+        }
+        if constexpr (RETIRE) {
+          if (__all(famax + ffmax <= ARM_RETIRE)) {
+            PROF_DO(armstop = it + 1);
+            it++;
+            break;
+          }
+        }
+        if constexpr (FRETIRE) {
+          if (__all(ffmax <= ARM_RETIRE)) {
+            fret = true;
+            it++;
+            break;
+          }
         }
       }
       if constexpr (FRETIRE) {
-        if (__all(ffmax <= ARM_RETIRE)) {
-          fret = true;
-          it++;
-          break;
-        }
-      }
-    }
-    if constexpr (FRETIRE) {
-      // without F, nothing reads v_arm in these sweeps: E's steps move it once afterwards
-      float fE0[4];
+        // without F, nothing reads v_arm in these sweeps: E's steps move it once afterwards
+        float fE0[4];
 #pragma unroll
-      for (int ed = 0; ed < 4; ed++) fE0[ed] = fE[ed];
-      if (fret && !done)
-        for (; it < m.iterations; it++) {
-          float famax = 0.f, ffmax = 0.f;
-          if (sweep(std::true_type{}, std::false_type{}, famax, ffmax) * scale < m.tolerance) {
-            done = true;
-            break;
-          }
-          if constexpr (RETIRE) {
-            if (__all(famax <= ARM_RETIRE)) {
-#ifdef SOARM_PHASE_PROF
-              armstop = it + 1;
-#endif
-              it++;
+        for (int ed = 0; ed < 4; ed++) fE0[ed] = fE[ed];
+        if (fret && !done)
+          for (; it < m.iterations; it++) {
+            float famax = 0.f, ffmax = 0.f;
+            if (sweep(std::true_type{}, std::false_type{}, famax, ffmax) * scale < m.tolerance) {
+              done = true;
               break;
             }
+            if constexpr (RETIRE) {
+              if (__all(famax <= ARM_RETIRE)) {
+                PROF_DO(armstop = it + 1);
+                it++;
+                break;
+              }
+            }
+          }
+        if constexpr (!decltype(ext2)::value) {
+          if (fret) {
+            float df[4];
+#pragma unroll
+            for (int ed = 0; ed < 4; ed++) df[ed] = fE[ed] - fE0[ed];
+            const float mu = xq.eMu;
+            const float D[3] = {(df[0] + df[1]) + (df[2] + df[3]), mu * (df[0] - df[1]), mu * (df[2] - df[3])};
+            qvarm(xq.eWp, D);
           }
         }
-      if constexpr (!decltype(ext2)::value) {
-        if (fret) {
-          float df[4];
-#pragma unroll
-          for (int ed = 0; ed < 4; ed++) df[ed] = fE[ed] - fE0[ed];
-          const float mu = xq.eMu;
-          const float D[3] = {(df[0] + df[1]) + (df[2] + df[3]), mu * (df[0] - df[1]), mu * (df[2] - df[3])};
-          qvarm(xq.eWp, D);
-        }
+        // (no re-check of the retired frictionloss rows against the v_arm E / F kept moving
+        // (ADVICE r03): holding their 24 values through the retired sweeps for a check costs the
+        // kernel ~15 spilled VGPRs and 9% of its time (r04, measured; an applied verification
+        // sweep also takes the result one sweep past mj_solPGS's stopping point).  The effect of
+        // retiring them is bounded against the oracle's full-sweep PGS on envs with an extra
+        // contact by test_gpu_parity.test_one_substep_extra_contact_sweeps.)
       }
-      // (no re-check of the retired frictionloss rows against the v_arm E / F kept moving
-      // (ADVICE r03): holding their 24 values through the retired sweeps for a check costs the
-      // kernel ~15 spilled VGPRs and 9% of its time (r04, measured; an applied verification
-      // sweep also takes the result one sweep past mj_solPGS's stopping point).  The effect of
-      // retiring them is bounded against the oracle's full-sweep PGS on envs with an extra
-      // contact by test_gpu_parity.test_one_substep_extra_contact_sweeps.)
-    }
-    if constexpr (RETIRE) {
-      // the block-only sweeps hold far fewer values than the sweeps with the arm's rows:
-      // re-define the block's loop constants here (an empty asm per value) so they get
-      // registers of their own for this loop instead of the AGPR homes they were given
-      // under the first loop's pressure (one copy here, not an AGPR read per sweep)
-      if constexpr (PK::value) {
+      if constexpr (RETIRE) {
+        // the block-only sweeps hold far fewer values than the sweeps with the arm's rows:
+        // re-define the block's loop constants here (an empty asm per value) so they get
+        // registers of their own for this loop instead of the AGPR homes they were given
+        // under the first loop's pressure (one copy here, not an AGPR read per sweep)
 #pragma unroll
         for (int k = 0; k < FC; k++) {
           vpin(qA2030[k]), vpin(qA2131[k]), vpin(qhd01[k]), vpin(qhd23[k]), vpin(sA10[k]), vpin(sA32[k]);
@@ -2133,275 +1860,232 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
           for (int ed = 0; ed < 4; ed++) vpin(C01[k][ed]), vpin(C23[k][ed]), vpin(cfo[k][ed]);
         }
         vpin(ro01), vpin(ro23);
-      }
-      if (!done)
-        for (; it < m.iterations; it++) {
-          float unused = 0.f, unused2 = 0.f;
-          if (sweep(std::false_type{}, std::false_type{}, unused, unused2) * scale < m.tolerance) {
-            done = true;
-            break;
-          }
-        }
-    }
-#ifdef SOARM_PHASE_PROF
-    nsweep = done ? it + 1 : m.iterations;
-#endif
-    (void)done;
-    yblock_finish();
-    if constexpr (decltype(ext)::value) yext_finish(cE, hasE, cF, hasF, coupled);
-  };
-  const bool ypure = CON && NF == 1 && block_first && __all(nlim == 0 && nl == ncon && npost == 0);
-  // up to two extras: the first of two must be arm-only (arm-only pairs precede the cube's
-  // in pair order, so that is the common case), the last may touch the cube
-  const bool yext = CON && NF == 1 && !ypure && block_first &&
-                    __all(nlim == 0 && nl == ncon && npost <= 2 &&
-                          (npost < 2 || (int)L.at(xidx(0), F_FLAGS) == TOUCH_ARM));
-  const bool ycoupled = yext && __any(npost >= 1 && ((int)L.at(cE, F_FLAGS) & TOUCH_FREE));
-  const bool yext2 = yext && __any(npost == 2);
-  auto sweeps = [&](auto first) {
-    for (int it = 0; it < m.iterations; it++) {
-      float improvement = 0.f;
-      if constexpr (decltype(first)::value) {
-        fric_rows(improvement);  // same basic block as the register block: they interleave
-        block_rows(improvement);
-        limit_rows(improvement);
-        for (int j = 0; j < npost; j++) lds_contact(j < c0 - npre ? npre + j : c1 + j - (c0 - npre), improvement);
-        scratch_rows(improvement);
-      } else {
-        fric_rows(improvement);
-        limit_rows(improvement);
-        for (int c = 0; c < npre; c++) lds_contact(c, improvement);
-        block_rows(improvement);
-        for (int j = 0; j < npost; j++) lds_contact(j < c0 - npre ? npre + j : c1 + j - (c0 - npre), improvement);
-        scratch_rows(improvement);
-      }
-      if (improvement * scale < m.tolerance) {
-#ifdef SOARM_PHASE_PROF
-        nsweep = it + 1;
-#endif
-        break;
-      }
-    }
-  };
-  // ---- row-space PGS (RS kernel; see RS_MAXROW above).  Rows in mj_solPGS order: the NA dof
-  // frictionloss rows, the active limits, 4 pyramid edges per contact; NRB (compile time) bounds
-  // the rows of every env of the wave (rows past an env's own are zero rows: J = 0, so C's row and
-  // column are 0 and their steps are exact no-ops).  Lane r16 holds rows r16 (slot A) and 16 + r16
-  // (slot B, when NRB > 16).  v: the velocity after the warm start; on return, qacc.
-  auto rs_solve = [&](auto kat_c, auto kac_c) {
-    if constexpr (RS && NF == 1 && CON) {
-      using LY = RsLayout<NA, decltype(kat_c)::value, decltype(kac_c)::value>;
-      constexpr int NS = LY::NS, KAT = decltype(kat_c)::value, KAC = decltype(kac_c)::value;
-      const int r16 = L.lane & 15;
-      float* const Wl = L.rsw + L.col * RS_WENV;
-      // this lane's rows: slot A = CT edge r16, slot B = frictionloss row / AT edge / AC edge r16;
-      // kind 0 frictionloss, 1 pyramid edge, -1 none; c, ed: the edge's contact and edge index;
-      // qA / qB: the rows' step indices (their W rows in LDS)
-      const int cA = rs_nat + (r16 >> 2), qA = LY::CT0 + r16;
-      const int kindA = (r16 >> 2) < rs_nct ? 1 : -1;
-      int kindB = -1, cB = 0;
-      if (r16 < NA) {
-        kindB = 0;
-      } else if (r16 < LY::CT0) {
-        cB = (r16 - NA) >> 2, kindB = cB < rs_nat ? 1 : -1;
-      } else if (r16 < LY::CT0 + 4 * KAC) {
-        const int k = (r16 - LY::CT0) >> 2;
-        cB = rs_nat + rs_nct + k, kindB = k < rs_nac ? 1 : -1;
-      }
-      const int qB = r16 < LY::CT0 ? r16 : r16 + 16;
-      // row data: J (NV), aref, R, the warm-start force (the warm start above)
-      auto row_of = [&](int kind, int c, int ed, float (&J)[NV], float& ar, float& R, float& f) {
-#pragma unroll
-        for (int i = 0; i < NV; i++) J[i] = 0.f;
-        ar = 0.f, R = 1.f, f = 0.f;
-        if (kind == 0) {  // dof frictionloss row ed: J = e_ed
-#pragma unroll
-          for (int i = 0; i < NA; i++)
-            if (ed == i) {
-              J[i] = 1.f, ar = fa[i], R = fR[i];
-              // warm-start force (the Gram-form warm start's frictionloss branch)
-              const float fl = m.dof_frictionloss[i], jar = S.warm[i] - fa[i];
-              const float fs = (jar <= -fl * R) ? fl : (jar >= fl * R) ? -fl : -jar / R;
-              f = fl > 0.f ? fs : 0.f;
+        if (!done)
+          for (; it < m.iterations; it++) {
+            float unused = 0.f, unused2 = 0.f;
+            if (sweep(std::false_type{}, std::false_type{}, unused, unused2) * scale < m.tolerance) {
+              done = true;
+              break;
             }
-        } else if (kind == 1) {  // pyramid edge J_n +- mu J_t of contact c
-          const float mu = L.at(c, F_MU), s = (ed & 1) ? -mu : mu;
-          const int t = 12 * (1 + (ed >> 1));
-#pragma unroll
-          for (int i = 0; i < NV; i++) J[i] = fmaf(s, L.at(c, t + i), L.at(c, i));
-          ar = L.at(c, F_AREF + ed), R = L.at(c, F_R);
-          float jar = -ar;  // warm-start force: the edge's J qacc_warmstart - aref, if negative
-#pragma unroll
-          for (int i = 0; i < NV; i++) jar = fmaf(J[i], S.warm[i], jar);
-          f = jar < 0.f ? -jar / R : 0.f;
+          }
+      }
+      PROF_DO(nsweep = done ? it + 1 : m.iterations);
+      (void)done;
+      yblock_finish();
+      if constexpr (decltype(ext)::value) yext_finish(cE, hasE, cF, hasF, coupled);
+    };
+    const bool ypure = block_first && __all(nlim == 0 && nl == ncon && npost == 0);
+    // up to two extras: the first of two must be arm-only (arm-only pairs precede the cube's
+    // in pair order, so that is the common case), the last may touch the cube
+    const bool yext = !ypure && block_first &&
+                      __all(nlim == 0 && nl == ncon && npost <= 2 &&
+                            (npost < 2 || (int)L.at(xidx(0), F_FLAGS) == TOUCH_ARM));
+    const bool ycoupled = yext && __any(npost >= 1 && ((int)L.at(cE, F_FLAGS) & TOUCH_FREE));
+    const bool yext2 = yext && __any(npost == 2);
+    PROF_DO(pf_ypure = ypure, pf_yext = yext, pf_yext2 = yext2, pf_ycoupled = ycoupled);
+    // ---- row-space PGS (RS kernel; see RS_MAXROW above).  Rows in mj_solPGS order: the NA dof
+    // frictionloss rows, the active limits, 4 pyramid edges per contact; NRB (compile time) bounds
+    // the rows of every env of the wave (rows past an env's own are zero rows: J = 0, so C's row and
+    // column are 0 and their steps are exact no-ops).  Lane r16 holds rows r16 (slot A) and 16 + r16
+    // (slot B, when NRB > 16).  v: the velocity after the warm start; on return, qacc.
+    auto rs_solve = [&](auto kat_c, auto kac_c) {
+      if constexpr (RS) {
+        using LY = RsLayout<NA, decltype(kat_c)::value, decltype(kac_c)::value>;
+        constexpr int NS = LY::NS, KAT = decltype(kat_c)::value, KAC = decltype(kac_c)::value;
+        const int r16 = L.lane & 15;
+        float* const Wl = L.rsw + L.col * RS_WENV;
+        // this lane's rows: slot A = CT edge r16, slot B = frictionloss row / AT edge / AC edge r16;
+        // kind 0 frictionloss, 1 pyramid edge, -1 none; c, ed: the edge's contact and edge index;
+        // qA / qB: the rows' step indices (their W rows in LDS)
+        const int cA = rs_nat + (r16 >> 2), qA = LY::CT0 + r16;
+        const int kindA = (r16 >> 2) < rs_nct ? 1 : -1;
+        int kindB = -1, cB = 0;
+        if (r16 < NA) {
+          kindB = 0;
+        } else if (r16 < LY::CT0) {
+          cB = (r16 - NA) >> 2, kindB = cB < rs_nat ? 1 : -1;
+        } else if (r16 < LY::CT0 + 4 * KAC) {
+          const int k = (r16 - LY::CT0) >> 2;
+          cB = rs_nat + rs_nct + k, kindB = k < rs_nac ? 1 : -1;
         }
-      };
-      float JA[NV], JB[NV], WA[NV], WB[NV], arA, arB, RA, RB, fA, fB;
-      row_of(kindA, cA, r16 & 3, JA, arA, RA, fA);
-      row_of(kindB, cB, kindB == 0 ? r16 : (r16 - NA) & 3, JB, arB, RB, fB);
-      Mi.mul(JA, WA, false, true);  // (CT rows touch the free body alone)
-      Mi.mul(JB, WB, true, KAC > 0);
-      // W rows to LDS, by step (the 4 copies of a quad write identical values)
+        const int qB = r16 < LY::CT0 ? r16 : r16 + 16;
+        // row data: J (NV), aref, R, the warm-start force (the warm start above)
+        auto row_of = [&](int kind, int c, int ed, float (&J)[NV], float& ar, float& R, float& f) {
 #pragma unroll
-      for (int i = 0; i < NV; i++) Wl[qA * RS_WROW + i] = WA[i];
-      if (qB < NS)
+          for (int i = 0; i < NV; i++) J[i] = 0.f;
+          ar = 0.f, R = 1.f, f = 0.f;
+          if (kind == 0) {  // dof frictionloss row ed: J = e_ed
 #pragma unroll
-        for (int i = 0; i < NV; i++) Wl[qB * RS_WROW + i] = WB[i];
-      // AR_rr = J_r W_r + R_r
-      float ardA = RA, ardB = RB;
+            for (int i = 0; i < NA; i++)
+              if (ed == i) {
+                J[i] = 1.f, ar = fa[i], R = fR[i];
+                // warm-start force (the Gram-form warm start's frictionloss branch)
+                const float fl = m.dof_frictionloss[i], jar = S.warm[i] - fa[i];
+                const float fs = (jar <= -fl * R) ? fl : (jar >= fl * R) ? -fl : -jar / R;
+                f = fl > 0.f ? fs : 0.f;
+              }
+          } else if (kind == 1) {  // pyramid edge J_n +- mu J_t of contact c
+            const float mu = L.at(c, F_MU), s = (ed & 1) ? -mu : mu;
+            const int t = 12 * (1 + (ed >> 1));
 #pragma unroll
-      for (int i = 0; i < NV; i++) ardA = fmaf(JA[i], WA[i], ardA), ardB = fmaf(JB[i], WB[i], ardB);
-      const float iA = 1.f / ardA, iB = 1.f / ardB;
-      const float hdA = 0.5f * ardA, hdB = 0.5f * ardB;
-      wave_sync();
-      // the bound registers, broadcast over the env's row: -f_q (edges) and the frictionloss
-      // rows' lo - f, hi - f
-      float NF_[NS], NH_[NA];
-      auto bounds = [&]() {
+            for (int i = 0; i < NV; i++) J[i] = fmaf(s, L.at(c, t + i), L.at(c, i));
+            ar = L.at(c, F_AREF + ed), R = L.at(c, F_R);
+            float jar = -ar;  // warm-start force: the edge's J qacc_warmstart - aref, if negative
+#pragma unroll
+            for (int i = 0; i < NV; i++) jar = fmaf(J[i], S.warm[i], jar);
+            f = jar < 0.f ? -jar / R : 0.f;
+          }
+        };
+        float JA[NV], JB[NV], WA[NV], WB[NV], arA, arB, RA, RB, fA, fB;
+        row_of(kindA, cA, r16 & 3, JA, arA, RA, fA);
+        row_of(kindB, cB, kindB == 0 ? r16 : (r16 - NA) & 3, JB, arB, RB, fB);
+        Mi.mul(JA, WA, false, true);  // (CT rows touch the free body alone)
+        Mi.mul(JB, WB, true, KAC > 0);
+        // W rows to LDS, by step (the 4 copies of a quad write identical values)
+#pragma unroll
+        for (int i = 0; i < NV; i++) Wl[qA * RS_WROW + i] = WA[i];
+        if (qB < NS)
+#pragma unroll
+          for (int i = 0; i < NV; i++) Wl[qB * RS_WROW + i] = WB[i];
+        // AR_rr = J_r W_r + R_r
+        float ardA = RA, ardB = RB;
+#pragma unroll
+        for (int i = 0; i < NV; i++) ardA = fmaf(JA[i], WA[i], ardA), ardB = fmaf(JB[i], WB[i], ardB);
+        const float iA = 1.f / ardA, iB = 1.f / ardB;
+        const float hdA = 0.5f * ardA, hdB = 0.5f * ardB;
+        wave_sync();
+        // the bound registers, broadcast over the env's row: -f_q (edges) and the frictionloss
+        // rows' lo - f, hi - f
+        float NF_[NS], NH_[NA];
+        auto bounds = [&]() {
+          sfor<NS>([&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+            const float fq = -rowbcast<LY::lane(q)>(LY::slot(q) == 0 ? fA : fB);
+            if constexpr (q < NA) {
+              const float fl = m.dof_frictionloss[q];
+              NF_[q] = fq - fl, NH_[q] = fq + fl;
+            } else {
+              NF_[q] = fq;
+            }
+          });
+        };
+        // v = qacc_smooth + sum_q W_q f_q (lane i < NV sums dof i, the row broadcasts it); f_q from the
+        // bound registers (NH_ = fl - f on the frictionloss rows, NF_ = -f on the others)
+        auto vel = [&]() {
+          float acc = 0.f;
+          const int di = r16 < NV ? r16 : 0;
+#pragma unroll
+          for (int q = 0; q < NS; q++)
+            acc = fmaf(Wl[q * RS_WROW + di], q < NA ? m.dof_frictionloss[q] - NH_[q] : -NF_[q], acc);
+          sfor<NV>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            v[i] = S.qacc_s[i] + rowbcast<i>(acc);
+          });
+        };
+        // the warm start in row space (the Gram-form block above is skipped on these waves): every
+        // row's warm force (row_of), v, and the dual cost against f = 0, summed over the env's rows
+        bounds();
+        vel();
+        float jvA = -arA, jvB = -arB, jqA = -arA, jqB = -arB;
+#pragma unroll
+        for (int i = 0; i < NV; i++) {
+          jvA = fmaf(JA[i], v[i], jvA), jvB = fmaf(JB[i], v[i], jvB);
+          jqA = fmaf(JA[i], S.qacc_s[i], jqA), jqB = fmaf(JB[i], S.qacc_s[i], jqB);
+        }
+        // dual cost: sum_r 0.5 f_r (J_r v - aref_r + R_r f_r) + 0.5 f_r (J_r qacc_smooth - aref_r)
+        const float wcost = rowsum16(0.5f * fA * (jvA + RA * fA) + 0.5f * fA * jqA +
+                                     (0.5f * fB * (jvB + RB * fB) + 0.5f * fB * jqB));
+        const bool rej = wcost > 0.f;  // worse than no warm start: f = 0, v = qacc_smooth
+        if (__any(rej)) {              // (wave-uniform: the broadcasts run on every row)
+          fA = rej ? 0.f : fA, fB = rej ? 0.f : fB;
+          bounds();
+#pragma unroll
+          for (int i = 0; i < NV; i++) v[i] = rej ? S.qacc_s[i] : v[i];
+          jvA = rej ? jqA : jvA, jvB = rej ? jqB : jvB;
+        }
+        f2 sA = f2{-fmaf(RA, fA, jvA) * iA, 0.f}, sB = f2{-fmaf(RB, fB, jvB) * iB, 0.f};
+        // the scaled matrix: C[r][q] = -J_r W_q / AR_rr, C[r][r] = -1, as (C, G) pairs: G is the row's
+        // own-step indicator, so the second accumulator takes the row's force step exactly (the stop
+        // test's Delta f_r; it was u_r - Delta s_r from an off-diagonal accumulator, whose fp32
+        // cancellation stopped an ill-conditioned env 22 sweeps early, 3.3e-3 m/s off -- r05); only
+        // the blocks a step updates
+        f2 CA[NS], CB[NS];
         sfor<NS>([&](auto qc) {
           constexpr int q = decltype(qc)::value;
-          const float fq = -rowbcast<LY::lane(q)>(LY::slot(q) == 0 ? fA : fB);
-          if constexpr (q < NA) {
-            const float fl = m.dof_frictionloss[q];
-            NF_[q] = fq - fl, NH_[q] = fq + fl;
-          } else {
-            NF_[q] = fq;
+          constexpr bool UA = LY::upd_a(q), UB = LY::upd_b(q);
+          f2 a = f2{0.f, 0.f};
+#pragma unroll
+          for (int i = 0; i < NV; i++)
+            a = fma2(f2{UA ? JA[i] : 0.f, UB ? JB[i] : 0.f}, splat2(Wl[q * RS_WROW + i]), a);
+          const float ca = -a.x * iA, cb = -a.y * iB;
+          CA[q] = qA == q ? f2{-1.f, 1.f} : f2{ca, 0.f};
+          CB[q] = qB == q ? f2{-1.f, 1.f} : f2{cb, 0.f};
+          // (the W rows of two steps in flight at a time: hoisting every step's 12 LDS loads to
+          // the top would hold hundreds of values)
+          if constexpr (q & 1) __builtin_amdgcn_sched_barrier(0);
+        });
+        float scale = m.pgs_scale, tol = m.tolerance;
+        int iters = m.iterations;
+        // (loaded once: the sweeps' asm statements keep LICM from hoisting the model loads, which would
+        // otherwise be re-issued and waited for in every sweep)
+        asm volatile("" : "+s"(iters), "+s"(scale), "+s"(tol));
+        bool done = false;
+        PHASE_T(rp0);  // (the RS solve's split: prof_rs_split)
+        PROF_DECL(int wsw = 0);
+        for (int it = 0; it < iters; it++) {
+          PROF_DO(wsw = it + 1);
+          if (!done) {
+            PROF_DO(nsweep = it + 1);
+            const float s0A = sA.x, s0B = sB.x;
+            sA.y = 0.f, sB.y = 0.f;
+            rs_sweep<NA, LY>(sA, sB, CA, CB, NF_, NH_);
+            // improvement = sum_r AR_rr / 2 Delta f_r (s0 + s1)_r, Delta f_r = the row's own step (y)
+            float P = hdA * sA.y * (s0A + sA.x);
+            P = fmaf(hdB * sB.y, s0B + sB.x, P);
+            done = rowsum16(P) * scale < tol;
           }
-        });
-      };
-      // v = qacc_smooth + sum_q W_q f_q (lane i < NV sums dof i, the row broadcasts it); f_q from the
-      // bound registers (NH_ = fl - f on the frictionloss rows, NF_ = -f on the others)
-      auto vel = [&]() {
-        float acc = 0.f;
-        const int di = r16 < NV ? r16 : 0;
-#pragma unroll
-        for (int q = 0; q < NS; q++)
-          acc = fmaf(Wl[q * RS_WROW + di], q < NA ? m.dof_frictionloss[q] - NH_[q] : -NF_[q], acc);
-        sfor<NV>([&](auto ic) {
-          constexpr int i = decltype(ic)::value;
-          v[i] = S.qacc_s[i] + rowbcast<i>(acc);
-        });
-      };
-      // the warm start in row space (the Gram-form block above is skipped on these waves): every
-      // row's warm force (row_of), v, and the dual cost against f = 0, summed over the env's rows
-      bounds();
-      vel();
-      float jvA = -arA, jvB = -arB, jqA = -arA, jqB = -arB;
-#pragma unroll
-      for (int i = 0; i < NV; i++) {
-        jvA = fmaf(JA[i], v[i], jvA), jvB = fmaf(JB[i], v[i], jvB);
-        jqA = fmaf(JA[i], S.qacc_s[i], jqA), jqB = fmaf(JB[i], S.qacc_s[i], jqB);
-      }
-      // dual cost: sum_r 0.5 f_r (J_r v - aref_r + R_r f_r) + 0.5 f_r (J_r qacc_smooth - aref_r)
-      const float wcost = rowsum16(0.5f * fA * (jvA + RA * fA) + 0.5f * fA * jqA +
-                                   (0.5f * fB * (jvB + RB * fB) + 0.5f * fB * jqB));
-      const bool rej = wcost > 0.f;  // worse than no warm start: f = 0, v = qacc_smooth
-      if (__any(rej)) {              // (wave-uniform: the broadcasts run on every row)
-        fA = rej ? 0.f : fA, fB = rej ? 0.f : fB;
-        bounds();
-#pragma unroll
-        for (int i = 0; i < NV; i++) v[i] = rej ? S.qacc_s[i] : v[i];
-        jvA = rej ? jqA : jvA, jvB = rej ? jqB : jvB;
-      }
-      f2 sA = f2{-fmaf(RA, fA, jvA) * iA, 0.f}, sB = f2{-fmaf(RB, fB, jvB) * iB, 0.f};
-      // the scaled matrix: C[r][q] = -J_r W_q / AR_rr, C[r][r] = -1, as (C, G) pairs: G is the row's
-      // own-step indicator, so the second accumulator takes the row's force step exactly (the stop
-      // test's Delta f_r; it was u_r - Delta s_r from an off-diagonal accumulator, whose fp32
-      // cancellation stopped an ill-conditioned env 22 sweeps early, 3.3e-3 m/s off -- r05); only
-      // the blocks a step updates
-      f2 CA[NS], CB[NS];
-      sfor<NS>([&](auto qc) {
-        constexpr int q = decltype(qc)::value;
-        constexpr bool UA = LY::upd_a(q), UB = LY::upd_b(q);
-        f2 a = f2{0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < NV; i++)
-          a = fma2(f2{UA ? JA[i] : 0.f, UB ? JB[i] : 0.f}, splat2(Wl[q * RS_WROW + i]), a);
-        const float ca = -a.x * iA, cb = -a.y * iB;
-        CA[q] = qA == q ? f2{-1.f, 1.f} : f2{ca, 0.f};
-        CB[q] = qB == q ? f2{-1.f, 1.f} : f2{cb, 0.f};
-        // (the W rows of two steps in flight at a time: hoisting every step's 12 LDS loads to
-        // the top would hold hundreds of values)
-        if constexpr (q & 1) __builtin_amdgcn_sched_barrier(0);
-      });
-      float scale = m.pgs_scale, tol = m.tolerance;
-      int iters = m.iterations;
-      // (loaded once: the sweeps' asm statements keep LICM from hoisting the model loads, which would
-      // otherwise be re-issued and waited for in every sweep)
-      asm volatile("" : "+s"(iters), "+s"(scale), "+s"(tol));
-      bool done = false;
-#ifdef SOARM_PHASE_PROF
-      // (the RS solve's split, in the Newton profiler's slots: PGS builds leave them unused)
-      // [8] setup, [9] sweeps, [10] final qacc, summed over waves; [11] waves; [16] sum of wave sweeps
-      const long long rp0 = clock64();
-      int wsw = 0;
-#endif
-      for (int it = 0; it < iters; it++) {
-#ifdef SOARM_PHASE_PROF
-        wsw = it + 1;
-#endif
-        if (!done) {
-#ifdef SOARM_PHASE_PROF
-          nsweep = it + 1;
-#endif
-          const float s0A = sA.x, s0B = sB.x;
-          sA.y = 0.f, sB.y = 0.f;
-          rs_sweep<NA, LY>(sA, sB, CA, CB, NF_, NH_);
-          // improvement = sum_r AR_rr / 2 Delta f_r (s0 + s1)_r, Delta f_r = the row's own step (y)
-          float P = hdA * sA.y * (s0A + sA.x);
-          P = fmaf(hdB * sB.y, s0B + sB.x, P);
-          done = rowsum16(P) * scale < tol;
+          if (__all(done)) break;
         }
-        if (__all(done)) break;
+        PHASE_T(rp1);
+        // qacc = qacc_smooth + sum_q W_q f_q (NH_ = fl - f on the frictionloss rows, NF_ = -f on the
+        // others): lane i < NV sums dof i, then the row broadcasts it
+        vel();
+        PROF_DO(prof_rs_split(e, rp0, rp1, wsw));
       }
-#ifdef SOARM_PHASE_PROF
-      const long long rp1 = clock64();
-#endif
-      // qacc = qacc_smooth + sum_q W_q f_q (NH_ = fl - f on the frictionloss rows, NF_ = -f on the
-      // others): lane i < NV sums dof i, then the row broadcasts it
-      vel();
-#ifdef SOARM_PHASE_PROF
-      if ((threadIdx.x & 63) == 0 && WPH_ID() < WPH_MAXW) {
-        const long long rp2 = clock64();
-        WPH_ADD(77, rp0 - g_pgs_prof[8 * e]);
-        WPH_ADD(78, rp1 - rp0);
-        WPH_ADD(79, rp2 - rp1);
-        WPH_ADD(80, 1);
-        WPH_ADD(81, wsw);
+    };
+    // wave-uniform choice: separate copies of the loop, no branch inside the sweep
+    if constexpr (RS) {
+      if (rs_fast) {
+        using Z = std::integral_constant<int, 0>;
+        using O = std::integral_constant<int, 1>;
+        int kat = __any(rs_nat >= 1) ? 1 : 0, kac = __any(rs_nac >= 1) ? 1 : 0;
+        PROF_DO(if (g_rs_force11) kat = kac = 1);  // (diagnostic: every RS wave in the (1, 1) layout)
+        if (kac == 1 && kat == 1)
+          rs_solve(O{}, O{});
+        else if (kac == 1)
+          rs_solve(Z{}, O{});
+        else if (kat == 1)
+          rs_solve(O{}, Z{});
+        else
+          rs_solve(Z{}, Z{});
+      } else {
+        sweeps(std::false_type{});
       }
-#endif
-    }
-  };
-  // wave-uniform choice: separate copies of the loop, no branch inside the sweep
-  if constexpr (RS) {
-    if (rs_fast) {
-      using Z = std::integral_constant<int, 0>;
-      using O = std::integral_constant<int, 1>;
-      int kat = __any(rs_nat >= 1) ? 1 : 0, kac = __any(rs_nac >= 1) ? 1 : 0;
-#ifdef SOARM_PHASE_PROF
-      if (g_rs_force11) kat = kac = 1;  // (diagnostic: every RS wave in the (1, 1) layout)
-#endif
-      if (kac == 1 && kat == 1)
-        rs_solve(O{}, O{});
-      else if (kac == 1)
-        rs_solve(Z{}, O{});
-      else if (kat == 1)
-        rs_solve(O{}, Z{});
-      else
-        rs_solve(Z{}, Z{});
+    } else if (ypure) {
+      ysweeps(std::false_type{}, std::false_type{}, std::false_type{});
+    } else if (yext && yext2 && ycoupled) {
+      ysweeps(std::true_type{}, std::true_type{}, std::true_type{});
+    } else if (yext && yext2) {
+      ysweeps(std::true_type{}, std::false_type{}, std::true_type{});
+    } else if (yext && ycoupled) {
+      ysweeps(std::true_type{}, std::true_type{}, std::false_type{});
+    } else if (yext) {
+      ysweeps(std::true_type{}, std::false_type{}, std::false_type{});
+    } else if (block_first) {
+      sweeps(std::true_type{});
     } else {
       sweeps(std::false_type{});
     }
-  } else if (ypure) {
-    ysweeps(std::false_type{}, std::false_type{}, std::false_type{});
-  } else if (yext && yext2 && ycoupled) {
-    ysweeps(std::true_type{}, std::true_type{}, std::true_type{});
-  } else if (yext && yext2) {
-    ysweeps(std::true_type{}, std::false_type{}, std::true_type{});
-  } else if (yext && ycoupled) {
-    ysweeps(std::true_type{}, std::true_type{}, std::false_type{});
-  } else if (yext) {
-    ysweeps(std::true_type{}, std::false_type{}, std::false_type{});
   } else if (block_first) {
     sweeps(std::true_type{});
   } else {
@@ -2439,15 +2123,13 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
 #pragma unroll
     for (int i = 0; i < 3; i++) S.ee[i] = L.kp(k++);
   }
-#ifdef SOARM_PHASE_PROF
-  if (e < 65536)
+  PROF_DO(if (e < 65536)
     g_pgs_prof[8 * e + 1] = clock64(), g_pgs_prof[8 * e + 2] = nsweep,
-    g_pgs_prof[8 * e + 3] = (ypure ? 0 : yext ? 1 : block_first ? 2 : 3) | (npost > 0 && npost_free ? 16 : 0) |
+    g_pgs_prof[8 * e + 3] = (pf_ypure ? 0 : pf_yext ? 1 : block_first ? 2 : 3) | (npost > 0 && npost_free ? 16 : 0) |
                             (min(npost, 3) << 8) | (min(nfree_x, 3) << 12) | ((nl > 5) << 16) | ((nlim > 0) << 17) |
                             ((nl != ncon) << 18) | ((long long)min(armstop, 255) << 20) |
-                            ((long long)(yext ? 4 + 2 * yext2 + ycoupled : 0) << 28) | ((long long)(RS && !rs_fast) << 40) | ((long long)rs_why << 41),
-    g_pgs_prof[8 * e + 4] = nlim, g_pgs_prof[8 * e + 5] = ncon;
-#endif
+                            ((long long)(pf_yext ? 4 + 2 * pf_yext2 + pf_ycoupled : 0) << 28) | ((long long)(RS && !rs_fast) << 40) | ((long long)rs_why << 41),
+    g_pgs_prof[8 * e + 4] = nlim, g_pgs_prof[8 * e + 5] = ncon);
 
   // ---- qacc and qfrc_constraint = J' f
 #pragma unroll

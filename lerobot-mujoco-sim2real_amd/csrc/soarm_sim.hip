@@ -1106,7 +1106,7 @@ int sim_step(sim_batch* b, const sim_state* s, const float* action, int frame_sk
         const TraceRange tr_("substep");
         prof_mark(b, 2, q);
         auto kern = s->qfrc_applied ? k_substep<NA, NF, true, SOL> : k_substep<NA, NF, false, SOL>;
-        int epb = 64 / lpe<NF>();  // envs per 64-thread workgroup
+        int epb = 64 / QUAD_LPE;  // envs per 64-thread workgroup
         if constexpr (NF == 1 && SOL == SIM_SOL_PGS) {
           if (rs) {
             kern = s->qfrc_applied ? k_substep<NA, NF, true, SOL, true> : k_substep<NA, NF, false, SOL, true>;

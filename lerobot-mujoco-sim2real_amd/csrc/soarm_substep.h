@@ -8,31 +8,6 @@
 
 namespace soarm {
 
-#ifdef SOARM_PHASE_PROF
-// diagnostic build: summed wave cycles per k_substep phase
-//   [0] state load + checks, [1] kinematics..smooth forces, [2] constraint rows,
-//   [3] PGS sweeps, [4] qacc/fcon + Euler + obs + geom poses, [5] waves,
-//   [6] sum over envs of PGS sweeps, [7] env count, [8] max wave cycles,
-//   [9] waves on the register fast path, [10] max wave PGS cycles,
-//   [11] sum over waves of the wave's max sweep count, [12] waves with an active
-//   joint limit, [13] waves with a contact outside the register block, [14] waves
-//   with more than LDS_CON contacts, [15] max contacts of an env, [16] rows: up to
-//   the built contact rows, [17] rows: warm start + cost, [18] rows: block setup
-//   [19..22] waves per sweep variant (y-pure, y+arm slot, block-first general, other),
-//   [23..26] max wave cycles per variant, [27] waves with a non-block contact on the free body
-//   [28..42] wave cycles between consecutive fine stamps (g_stamp, see PSTAMP sites)
-// (accumulated per wave in g_wphase, soarm_pgs.h; this is the layout)
-//                                          [53..56] contact-row build split (g_rowprof),
-                                            // [57] waves that retired the arm rows, [58] sum of their retire sweeps,
-                                            // [59] / [60] max wave cycles of the waves that did not / did retire
-                                            // y+arm slot waves by (F slot, E coupled to the cube) = 2 F + coupled:
-                                            // [61..64] waves, [65..68] max wave cycles, [69..72] sum of PGS
-                                            // cycles, [73..76] sum of the arm-retire sweep (0: not retired)
-#define PHASE_T(v) const long long v = clock64()
-#else
-#define PHASE_T(v)
-#endif
-
 // one mj_forward (position + velocity + acceleration stages); the contacts
 // (cbuf/ccount, may be null) were produced by k_collide from this substep's positions
 template <int NA, int NF, bool CON, int SOL, bool RS = false>
@@ -135,9 +110,9 @@ __global__ __launch_bounds__(64) void k_substep(const DModel* __restrict__ dm, i
                                                 const int* __restrict__ ccount,
                                                 uint32_t* __restrict__ pmask,
                                                 float* __restrict__ gpose, const float* gpose_in) {
-  // envs per workgroup: lpe<NF>() lanes per env (soarm_pgs.h) run the same per-env code; the RS
+  // envs per workgroup: QUAD_LPE lanes per env (soarm_pgs.h) run the same per-env code; the RS
   // kernel has 16 per env (4 quads)
-  constexpr int COLS = RS ? RS_EPW : 64 / lpe<NF>();
+  constexpr int COLS = RS ? RS_EPW : 64 / QUAD_LPE;
   constexpr int LPE = 64 / COLS;
   const int e = xcd_block() * COLS + (int)threadIdx.x / LPE;
   static_assert(!RS || (NF == 1 && SOL == SIM_SOL_PGS), "RS kernel: PGS, scene with a free body");
@@ -156,7 +131,7 @@ __global__ __launch_bounds__(64) void k_substep(const DModel* __restrict__ dm, i
   __shared__ float s_lim[NA * LF][COLS];
   __shared__ float s_keep[keep_floats<NA, NF>()][COLS];
   // contact list (quad), y-sweep slots; Newton: its line-search rows (8 per LDS contact)
-  __shared__ float s_ext[NF == 1 ? XS_EXT : (lpe<NF>() == 4 ? XS_LIST + (SOL == SIM_SOL_NEWTON ? 12 * LDS_CON : 0) : 1)][COLS];
+  __shared__ float s_ext[NF == 1 ? XS_EXT : XS_LIST + (SOL == SIM_SOL_NEWTON ? 12 * LDS_CON : 0)][COLS];
   RowLds L{&s_rows[0][0], &s_lim[0][0], NF == 1 ? &s_keep[0][0] : nullptr, &s_ext[0][0], (int)threadIdx.x,
            (int)threadIdx.x / LPE, COLS};
   __shared__ __attribute__((aligned(16))) float s_rsw[RS ? COLS * RS_WENV : 1];  // row-space W rows
@@ -189,26 +164,29 @@ __global__ __launch_bounds__(64) void k_substep(const DModel* __restrict__ dm, i
   PairMask pm;
   if (use) pm.load(pmask, m, n, e);  // (stays zero otherwise: no contact list)
   if (use && reset) qpos0_contacts(m, const_cast<float*>(cbuf), n, e, pm);
-#ifdef SOARM_PHASE_PROF
   PHASE_T(t1);
-  PSTAMP(0);
-  S.kinematics();
-  PSTAMP(1);
-  S.com_crb();
-  PSTAMP(2);
-  S.factor();
-  PSTAMP(3);
-  S.smooth_forces();
-  PSTAMP(4);
+  int ncon;
+  if constexpr (PHASE_PROF) {  // forward(), with a stamp after each stage
+    PSTAMP(0);
+    S.kinematics();
+    PSTAMP(1);
+    S.com_crb();
+    PSTAMP(2);
+    S.factor();
+    PSTAMP(3);
+    S.smooth_forces();
+    PSTAMP(4);
+  }
   PHASE_T(t2);
-  PSTAMP(5);
-  pm.hold();
-  if (AP) S.add_applied(st.qfrc_applied, n, e);
-  int ncon = solve_constraints<NA, NF, true, SOL, RS>(S, use ? cbuf : nullptr, use ? ccount : nullptr, pmask, n, e, L, cr, pm);
-#else
-  int ncon = forward<NA, NF, true, SOL, RS>(S, use ? cbuf : nullptr, use ? ccount : nullptr, pmask, n, e, L, cr,
-                                        AP ? st.qfrc_applied : nullptr, pm);
-#endif
+  if constexpr (PHASE_PROF) {
+    PSTAMP(5);
+    pm.hold();
+    if (AP) S.add_applied(st.qfrc_applied, n, e);
+    ncon = solve_constraints<NA, NF, true, SOL, RS>(S, use ? cbuf : nullptr, use ? ccount : nullptr, pmask, n, e, L, cr, pm);
+  } else {
+    ncon = forward<NA, NF, true, SOL, RS>(S, use ? cbuf : nullptr, use ? ccount : nullptr, pmask, n, e, L, cr,
+                                          AP ? st.qfrc_applied : nullptr, pm);
+  }
   if (S.acc_bad()) {
     S.soft_reset(SIM_ST_BADQACC);
     store_state(S, st, n, e);
@@ -220,7 +198,7 @@ __global__ __launch_bounds__(64) void k_substep(const DModel* __restrict__ dm, i
   }
   PSTAMP(10);
   if constexpr (SOL == SIM_SOL_NEWTON) {
-    if ((threadIdx.x & (lpe<NF>() - 1)) == 0) {
+    if ((threadIdx.x & (QUAD_LPE - 1)) == 0) {
       uint32_t* zh = (uint32_t*)(scratch + e) + (size_t)zhist_row<NA, NF>() * n;
       zh[0] = S.zfin, zh[n] = zh1;
     }
@@ -259,84 +237,9 @@ __global__ __launch_bounds__(64) void k_substep(const DModel* __restrict__ dm, i
   } else {
     PSTAMP(14);  // (the last substep writes no poses: both phases empty)
   }
-#ifdef SOARM_PHASE_PROF
   PHASE_T(t5);
   PSTAMP(15);
-  const long long p0 = g_pgs_prof[8 * e], p1 = g_pgs_prof[8 * e + 1];
-  const int nsw = (int)g_pgs_prof[8 * e + 2];
-  const bool anylim = __any(g_pgs_prof[8 * e + 4] > 0), anyslow = __any(g_pgs_prof[8 * e + 3] == 0),
-             anyovf = __any(g_pgs_prof[8 * e + 5] > LDS_CON), anyfree = __any(g_pgs_prof[8 * e + 3] & 16);
-  // (wave reductions first: one row per wave in g_wphase, no shared-address atomics)
-  auto wsum = [](int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-  };
-  int wmax = nsw, cmax = (int)g_pgs_prof[8 * e + 5];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) wmax = max(wmax, __shfl_xor(wmax, o)), cmax = max(cmax, __shfl_xor(cmax, o));
-  // per-lane census of lanes in waves on a non-y sweep: [43..46] npost 0..3+, [47..49] extras on
-  // the free body 0/1/2+, [50] > 5 contacts, [51] active limit, [52] overflow rows
-  const long long cv = g_pgs_prof[8 * e + 3];
-  const bool ny = (cv & 15) >= 2;
-  int census[10];
-#pragma unroll
-  for (int k = 0; k < 4; k++) census[k] = wsum(ny && ((cv >> 8) & 3) == k);
-#pragma unroll
-  for (int k = 0; k < 3; k++) census[4 + k] = wsum(ny && min((int)((cv >> 12) & 3), 2) == k);
-  census[7] = wsum(ny && ((cv >> 16) & 1)), census[8] = wsum(ny && ((cv >> 17) & 1)),
-  census[9] = wsum(ny && ((cv >> 18) & 1));
-  const int nsw_sum = wsum(nsw), lanes = wsum(1);
-  int why[7];
-#pragma unroll
-  for (int k = 0; k < 7; k++) why[k] = wsum((int)((cv >> (41 + k)) & 1));
-  if ((threadIdx.x & 63) == 0 && WPH_ID() < WPH_MAXW) {
-    WPH_MAX(15, cmax);
-    WPH_ADD(6, nsw_sum);
-    WPH_ADD(7, lanes);
-#pragma unroll
-    for (int k = 0; k < 10; k++) WPH_ADD(43 + k, census[k]);
-    WPH_ADD(0, t1 - t0);
-    WPH_ADD(1, t2 - t1);
-    WPH_ADD(2, p0 - t2);
-    WPH_ADD(3, p1 - p0);
-    WPH_ADD(4, t5 - p1);
-    WPH_MAX(8, t5 - t0);
-    {
-      int var = (int)g_pgs_prof[8 * e + 3] & 15;
-      WPH_ADD(9, var == 0);
-      WPH_ADD(19 + var, 1);
-      WPH_MAX(23 + var, t5 - t0);
-    }
-    WPH_ADD(27, anyfree);
-    for (int k = 0; k < 15; k++) WPH_ADD(28 + k, g_stamp[16 * e + k + 1] - g_stamp[16 * e + k]);
-    for (int k = 0; k < 4; k++) WPH_ADD(53 + k, g_rowprof[4 * e + k]);
-    WPH_ADD(16, g_pgs_prof[8 * e + 6] - t2);
-    WPH_ADD(17, g_pgs_prof[8 * e + 7] - g_pgs_prof[8 * e + 6]);
-    WPH_ADD(18, p0 - g_pgs_prof[8 * e + 7]);
-    WPH_ADD(12, anylim);
-    WPH_ADD(13, anyslow);
-    WPH_ADD(14, anyovf);
-    WPH_MAX(10, p1 - p0);
-    WPH_ADD(11, wmax);
-    WPH_ADD(5, 1);
-    if ((cv >> 40) & 1) {
-      WPH_ADD(82, 1), WPH_MAX(83, t5 - t0), WPH_ADD(84, t5 - t0);
-#pragma unroll
-      for (int k = 0; k < 7; k++) WPH_ADD(85 + k, why[k]);
-    }
-    const int ast = (int)((g_pgs_prof[8 * e + 3] >> 20) & 255);
-    if (ast) WPH_ADD(57, 1), WPH_ADD(58, ast);
-    WPH_MAX(ast ? 60 : 59, t5 - t0);
-    const int xv = (int)((g_pgs_prof[8 * e + 3] >> 28) & 7);
-    if (xv >= 4) {
-      WPH_ADD(61 + xv - 4, 1);
-      WPH_MAX(65 + xv - 4, t5 - t0);
-      WPH_ADD(69 + xv - 4, p1 - p0);
-      WPH_ADD(73 + xv - 4, ast);
-    }
-  }
-#endif
+  PROF_DO(prof_substep_end(e, t0, t1, t2, t5, LDS_CON));
 }
 
 }  // namespace soarm

@@ -485,3 +485,48 @@ def test_cpu_soft_reset_contact_scene_limit_at_qpos0(cpu_lib):
     np.testing.assert_allclose(to_np(S.qpos).T[bad], st["qpos"][bad], atol=5e-6)
     dv = np.abs(to_np(S.qvel).T - st["qvel"]).max(1)
     assert dv[bad].max() < 1e-5, dv[bad]
+
+
+ACC_BAD_ENVS = [1, 6, 17, 30, 63]  # share RS waves (4 envs) and quad waves (16 envs) with healthy envs
+
+
+def check_acc_bad_retry_contact_scene(make_sim, load_state):
+    """One substep of the pick scene (conftest.limit_qpos0_model: 4 resting contacts and an active
+    limit row at qpos0), 64 envs, with a finite qfrc_applied of 1e9 N m on the shoulder-pan dof of
+    the envs ACC_BAD_ENVS: qacc there is ~1e9 / M_00 > 1e10 (M_00 < 0.1 kg m^2), so mj_checkAcc trips
+    on exactly those envs.  They soft-reset (ST_BADQACC), their qfrc_applied rows are zeroed and
+    mj_forward runs again at qpos0, contacts included, beside envs that keep their first solve.
+    Bars: test_soft_reset_contact_scene_limit_at_qpos0's."""
+    import torch
+    from conftest import limit_qpos0_model, soft_reset_states
+    from lerobot_mujoco_sim2real_amd import abi
+    cm = limit_qpos0_model()
+    orc = Oracle(cm)
+    n, bad = 64, ACC_BAD_ENVS
+    st = soft_reset_states(cm, orc, n, [])
+    st["ncon"][:] = 0
+    app = np.zeros((n, cm.nv))
+    app[bad, 0] = 1e9
+    S = make_sim(cm, n)
+    load_state(S, st)
+    S.ncon.zero_()
+    S.enable_qfrc_applied().copy_(torch.as_tensor(app.T, dtype=torch.float32))
+    S.substeps(1)
+    orc.step(st, None, nsub=1, applied=app)
+    want = np.zeros(n, int)
+    want[bad] = abi.ST_BADQACC
+    assert (st["status"] == want).all(), st["status"]  # (the input: the oracle flags exactly `bad`)
+    stat = to_np(S.status).astype(int)
+    assert (stat == st["status"]).all(), stat
+    np.testing.assert_allclose(to_np(S.qpos).T, st["qpos"], atol=5e-6)
+    dv = np.abs(to_np(S.qvel).T - st["qvel"]).max(1)
+    print("acc-bad retry: qvel err p50 %.3g p99 %.3g max %.3g, bad envs max %.3g" %
+          (np.median(dv), np.percentile(dv, 99), dv.max(), dv[bad].max()))
+    assert_pct(dv, *QVEL_BARS, what="qvel")
+    assert dv[bad].max() < 1e-5, dv[bad]
+    assert to_np(S.ncon).sum() == st["ncon"].sum()
+    assert float(S.qfrc_applied[:, bad].abs().max()) == 0.0 and (app[bad] == 0).all()
+
+
+def test_cpu_acc_bad_retry_contact_scene(cpu_lib):
+    check_acc_bad_retry_contact_scene(make_sim, load_state)

@@ -13,7 +13,7 @@ import pytest
 
 from conftest import cube_qpos, fp32_noise_envelope, limit_qpos0_model, soft_reset_states
 from oracle import Oracle
-from test_cpu_backend import contact_point_split
+from test_cpu_backend import check_acc_bad_retry_contact_scene, contact_point_split
 
 pytestmark = pytest.mark.gpu
 
@@ -687,6 +687,16 @@ def test_soft_reset_contact_scene_limit_at_qpos0(gpu_lib, rs, monkeypatch):
     assert_pct(dv, *QVEL_BARS, what="qvel")
     assert dv[bad].max() < 1e-5, dv[bad]
     assert to_np(S.ncon).sum() - ncon0 == st["ncon"].sum() - ncon0
+
+
+@pytest.mark.parametrize("rs", ["1", "0"])
+def test_acc_bad_retry_contact_scene(gpu_lib, rs, monkeypatch):
+    """mj_checkAcc soft resets in the pick scene (test_cpu_backend.check_acc_bad_retry_contact_scene):
+    the bad envs' retry -- the qpos0 contacts, the whole constraint solve -- runs on a partly active
+    wave, the healthy envs of the wave keeping their first solve; rs = "1" the RS kernel, "0" the
+    quad kernel."""
+    monkeypatch.setenv("SOARM_RS", rs)
+    check_acc_bad_retry_contact_scene(make_sim, load_state)
 
 
 def test_golden_fixture_gpu(gpu_lib, arm_model_nocontact):
