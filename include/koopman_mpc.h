@@ -20,6 +20,8 @@
  *   sim_koopman_encode       Psi_o for M states (f64 MFMA encoder)
  *   sim_koopman_feedforward  Gr·r for every frame of a reference trajectory (f64 MFMA)
  *   sim_koopman_mpc_step     z0 = Psi_o(x); u0; a = clip(u0); u_prev = u0 (one launch)
+ *   sim_koopman_predict      the model's multi-step open-loop prediction of recorded trajectories
+ *                            and its error (evaluate(), train.py:35-87; one launch for all steps)
  *
  * Arithmetic is float64 throughout, as in the reference (model.double(), Koopman_MPC.py:263).
  * Device buffers are caller-owned; calls are asynchronous on the given stream (void* =
@@ -91,6 +93,33 @@ int sim_koopman_set_bilinear(sim_koopman* k, const double* A, const double* B, c
                              double q, double r);
 int sim_koopman_bilinear_step(sim_koopman* k, int n, const double* z0, const double* window, double* u_prev,
                               float* action, void* stream);
+
+/* Open-loop prediction and its error: how well the Koopman model predicts recorded trajectories.
+   This is what evaluate() (train.py:35-87) reports, through pred_and_eval_loss_old
+   (models/losses.py:132-173); relift = 0 is the latent rollout of pred_and_eval_loss_new
+   (models/losses.py:175-215).  One launch runs all T steps of n trajectories; the lifted state
+   stays in registers.
+
+   set_model: A [nz][nz], B [nz][u_dim]; Hhat [nz (j)][nz][u_dim] for DBKN (the array of
+   sim_koopman_set_bilinear, get_Hi_numpy: the u_z permutation is already in it) or NULL for DKUC.
+   Independent of sim_koopman_set_bilinear.  SIM_E_MODEL when the encoder and the model do not fit
+   the kernel's LDS plan (sim_koopman_predict then returns SIM_E_MODEL too).
+
+   predict: rows [T+1][n][ld] float32 row-major, x at columns x_off .. x_off + x_dim, u at
+   u_off .. u_off + u_dim (a rollout of the data generator, [u(5) | ee(3) | q(5)], is read in place
+   with ld = 13, x_off = 5, u_off = 0).  Float64 from the widened float32 inputs.  Per trajectory e:
+     x^_0 = x_0, z = Psi(x_0);
+     t = 0 .. T-1:  z <- A z + (B + sum_j z_j Hhat_j) u_t;  x^_{t+1} = z[:x_dim] (the reference's
+                    frozen decoder lC = [I | 0]);  relift != 0:  z <- Psi(x^_{t+1}).
+   pred [T+1][n][x_dim] (row 0 = x_0), or NULL.
+   err [2][n], or NULL: err[0][e] = sum_t sum_{d < npos} |x^_{t+1,d} - x_{t+1,d}|, err[1][e] the same
+   over d >= npos; deterministic (per-trajectory sums in a fixed order, no atomics).  The reference's
+   pred_loss / dis_loss / angle_loss are global means of these sums (npos = 3).
+   SIM_E_ARG: NULL k or rows, n < 0, T < 0, npos outside 0 .. x_dim, columns past ld, set_model not
+   called.  n == 0 is a no-op.  No allocation, copy or synchronisation: capturable in a graph. */
+int sim_koopman_set_model(sim_koopman* k, const double* A, const double* B, const double* Hhat);
+int sim_koopman_predict(sim_koopman* k, int n, int T, const float* rows, int ld, int x_off, int u_off,
+                        int relift, int npos, double* pred, double* err, void* stream);
 
 #ifdef __cplusplus
 }

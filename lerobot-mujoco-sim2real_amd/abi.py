@@ -20,6 +20,7 @@ ST_BADQPOS, ST_BADQVEL, ST_BADQACC, ST_CONOVERFLOW = 1, 2, 4, 8
 
 i32, f64 = C.c_int32, C.c_double
 ABI_VERSION = 2  # SIM_ABI_VERSION (include/soarm_sim.h)
+E_ARG, E_MODEL = -1, -2  # SIM_E_ARG, SIM_E_MODEL
 
 
 class _Versioned(C.Structure):
@@ -138,6 +139,7 @@ EXPORTS = [
     # include/koopman_mpc.h
     "sim_koopman_create", "sim_koopman_free", "sim_koopman_encode", "sim_koopman_feedforward",
     "sim_koopman_mpc_step", "sim_koopman_set_bilinear", "sim_koopman_bilinear_step",
+    "sim_koopman_set_model", "sim_koopman_predict",
 ]
 PROF_KINDS = ["step_fused", "collide", "substep", "geom"]
 
@@ -187,6 +189,8 @@ def load_lib(path=None):
     lib.sim_koopman_mpc_step.argtypes = [vp, ip, vp, vp, vp, vp, vp, vp]
     lib.sim_koopman_set_bilinear.argtypes = [vp, vp, vp, vp, ip, C.c_double, C.c_double]
     lib.sim_koopman_bilinear_step.argtypes = [vp, ip, vp, vp, vp, vp, vp]
+    lib.sim_koopman_set_model.argtypes = [vp, vp, vp, vp]
+    lib.sim_koopman_predict.argtypes = [vp, ip, ip, vp, ip, ip, ip, ip, ip, vp, vp, vp]
     for name in EXPORTS:
         if not hasattr(lib, name):
             raise RuntimeError(f"{p} does not export {name}")

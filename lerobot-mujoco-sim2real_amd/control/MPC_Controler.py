@@ -10,6 +10,8 @@ computed once on the host in float64) and every per-env evaluation runs in the H
 * :meth:`encode`       — Psi_o for a batch of states (``sim_koopman_encode``)
 * :meth:`feedforward`  — Gr · lifted reference window for every frame (``sim_koopman_feedforward``)
 * :meth:`step`         — one control step for n envs (``sim_koopman_mpc_step``)
+* :meth:`predict` / :meth:`evaluate` — the model's open-loop prediction of a device rollout and the
+  reference's evaluation metrics (``train.py:35-87``), all steps in one launch (``sim_koopman_predict``)
 
 A bilinear DBKN model (``net.H``, ``KoopmanBase.py:62-110``) linearises its input matrix at each
 frame's lifted state (``linearize_B``, ``:46-63``), so the QP differs per env and frame:
@@ -48,6 +50,10 @@ class MPCController:
         self.Ad = net.lA.weight.detach().double().cpu().numpy()
         self.Bd = net.lB.weight.detach().double().cpu().numpy()
         self.Nkoopman = self.Ad.shape[0]
+        # predict() reads x̂ = z[:x_dim]: the reference's frozen decoder (models/KoopmanBase.py:38-41)
+        lC = net.lC.weight.detach().double().cpu().numpy()
+        if lC.shape != (self.in_dim, self.Nkoopman) or not np.array_equal(lC, np.eye(self.in_dim, self.Nkoopman)):
+            raise ValueError("net.lC.weight must be the frozen decoder [I | 0]")
         self.H = horizon
         self.u_clip = u_clip
         self.u_eso = np.zeros(self.u_dim)
@@ -77,10 +83,18 @@ class MPCController:
         abi.check(self.lib, self.lib.sim_koopman_create(C.byref(d), self._w.ctypes.data_as(C.c_void_p),
                                                         self._g.ctypes.data_as(C.c_void_p), device,
                                                         C.byref(self._h)))
+        self._Ah = np.ascontiguousarray(self.Ad, np.float64)
+        self._Bh = np.ascontiguousarray(self.Bd, np.float64)
+        self._Hh = np.ascontiguousarray(np.stack(self.H_hat_list), np.float64) if self.bilinear else None  # [j][nz][nu]
+        # the open-loop prediction kernel (koopman_mpc.hip k_predict).  A model that only this kernel's
+        # LDS plan refuses (SIM_E_MODEL) still controls: predict() raises with the library's message
+        rc = self.lib.sim_koopman_set_model(self._h, self._Ah.ctypes.data_as(C.c_void_p),
+                                            self._Bh.ctypes.data_as(C.c_void_p),
+                                            self._Hh.ctypes.data_as(C.c_void_p) if self.bilinear else None)
+        self._predict_refused = self.lib.sim_last_error().decode() if rc == abi.E_MODEL else None
+        if rc != abi.E_MODEL:
+            abi.check(self.lib, rc)
         if self.bilinear:  # the per-env QP kernel (koopman_mpc.hip k_bilinear)
-            self._Ah = np.ascontiguousarray(self.Ad, np.float64)
-            self._Bh = np.ascontiguousarray(self.Bd, np.float64)
-            self._Hh = np.ascontiguousarray(np.stack(self.H_hat_list), np.float64)  # [j][nz][nu]
             abi.check(self.lib, self.lib.sim_koopman_set_bilinear(
                 self._h, self._Ah.ctypes.data_as(C.c_void_p), self._Bh.ctypes.data_as(C.c_void_p),
                 self._Hh.ctypes.data_as(C.c_void_p), int(self.MPC_type == "delta_mpc"), Q_WEIGHT, R_WEIGHT))
@@ -163,6 +177,42 @@ class MPCController:
         abi.check(self.lib, self.lib.sim_koopman_bilinear_step(self._h, n, _ptr(z0), _ptr(window), _ptr(u_prev),
                                                                _ptr(action), self._stream()))
         return action
+
+    def predict(self, rollout, relift=True, npos=3, want_pred=True):
+        """Open-loop prediction of a rollout [T+1, N, 13] fp32 (``rollout_device``: columns
+        [u | x]) in one launch, read in place (a strided or host input is first made contiguous on
+        the device): x̂_0 = x_0 and T model steps from it, re-lifting x̂ every step (``relift``, the
+        reference's ``pred_and_eval_loss_old``) or staying in the lifted space.  Returns
+        (pred [T+1, N, x_dim] float64 or None, err [2, N] float64): err[0] the summed |x̂ - x| over
+        the steps and dims < npos of each trajectory, err[1] over dims >= npos."""
+        torch = self.torch
+        if self._predict_refused is not None:
+            raise RuntimeError(f"soarm_sim error {abi.E_MODEL}: {self._predict_refused}")
+        r = torch.as_tensor(rollout)
+        ld = self.u_dim + self.in_dim
+        if r.dim() != 3 or r.shape[2] != ld or r.shape[0] < 1:
+            raise ValueError(f"predict: rollout must be [T+1, N, {ld}] ([u | x] rows); got {tuple(r.shape)}")
+        r = r.to(device=self.device, dtype=torch.float32).contiguous()
+        T, n = r.shape[0] - 1, r.shape[1]
+        pred = torch.empty((T + 1, n, self.in_dim), dtype=torch.float64, device=self.device) if want_pred else None
+        err = torch.empty((2, n), dtype=torch.float64, device=self.device)
+        abi.check(self.lib, self.lib.sim_koopman_predict(self._h, n, T, _ptr(r), ld, self.u_dim, 0, int(bool(relift)),
+                                                         int(npos), _ptr(pred), _ptr(err), self._stream()))
+        return pred, err
+
+    def evaluate(self, rollout, relift=True):
+        """The reference's ``evaluate()`` (``train.py:35-87``) on a device rollout [T+1, N, 13]:
+        dict(avg_error, dis_error, angle_error, all_preds) -- the mean absolute prediction error
+        over trajectories, the T steps and dims of all of x, of x[:3] (end-effector position) and of
+        x[3:] (joint angles), and the predictions [N, T+1, x_dim] (a device view)."""
+        npos = 3
+        pred, err = self.predict(rollout, relift=relift, npos=npos)
+        T, n = pred.shape[0] - 1, pred.shape[1]
+        if T < 1 or n < 1:
+            raise ValueError("evaluate: the rollout needs at least one step and one trajectory")
+        dis, ang = float(err[0].sum()), float(err[1].sum())
+        return dict(avg_error=(dis + ang) / (n * T * self.in_dim), dis_error=dis / (n * T * npos),
+                    angle_error=ang / (n * T * (self.in_dim - npos)), all_preds=pred.transpose(0, 1))
 
     # ------------------------------------------------------- reference single-env API
     def Psi_o(self, s):

@@ -6,7 +6,9 @@ Reference: ``models/KoopmanBase.py:12-60`` (``Koopmanlinear``, the ``DKUC`` mode
 is kept: the encoder ``x_encoder(x) = cat([x, MLP(x)])``, the Koopman matrices ``lA``
 (Nkoopman x Nkoopman, initialised as 0.9 x an orthogonalised Gaussian draw) and ``lB``
 (Nkoopman x u_dim), and the fixed decoder ``lC = [I | 0]``.  Training the model (``train.py``,
-``models/losses.py``) is out of scope.  Parameter names are the reference's
+``models/losses.py``) is out of scope; its evaluation -- the multi-step open-loop
+prediction error of ``evaluate()`` -- is :func:`open_loop_prediction` / :func:`prediction_errors`
+here and ``MPCController.predict`` / ``evaluate`` on the device.  Parameter names are the reference's
 (``x_encode_net.linear_{i}``, ``lA``, ``lB``, ``lC``, DBKN's ``H``), so a state_dict the reference
 saved loads with ``load_state_dict(..., strict=True)`` (``tests/test_koopman_mpc.py``).
 
@@ -113,6 +115,45 @@ def init_model(args):
     if args.model == "DBKN":
         return KoopmanBlinear(args.x_dim, args.u_dim, args.layers, bool(getattr(args, "u_z", False)))
     raise ValueError(f"Model {args.model} not implemented!")
+
+
+def open_loop_prediction(net, x, u, relift=True):
+    """Multi-step open-loop prediction of n recorded trajectories, float64 torch on x's device.
+
+    x [N, T+1, x_dim], u [N, >= T, u_dim].  x̂_0 = x_0, z = Psi(x_0); for t < T:
+    z ← koopman_operation(z, u_t) (A z + (B + Σ_j z_j Ĥ_j) u_t), x̂_{t+1} = z[:x_dim] (the frozen
+    decoder lC = [I | 0]) and, with ``relift``, z ← Psi(x̂_{t+1}).  ``relift=True`` is the
+    reference's ``pred_and_eval_loss_old`` (``models/losses.py:132-173``, what ``evaluate()``
+    runs, ``train.py:35-87``); ``relift=False`` its ``pred_and_eval_loss_new`` (``:175-215``).
+    Returns pred [N, T+1, x_dim].  The literal loop: the cross-check of
+    ``MPCController.predict`` (``koopman_mpc.hip`` ``k_predict``), which runs it in one launch."""
+    if net.lA.weight.dtype != torch.float64:
+        raise ValueError("open_loop_prediction runs in float64: call net.double() first (Koopman_MPC.py:263)")
+    with torch.no_grad():
+        x = torch.as_tensor(x).to(torch.float64)
+        u = torch.as_tensor(u).to(device=x.device, dtype=torch.float64)
+        xd = net.x_dim
+        xh = x[:, 0, :]
+        z = net.x_encoder(xh)
+        pred = [xh]
+        for t in range(x.shape[1] - 1):
+            z = net.koopman_operation(z, net.u_encoder(xh, u[:, t, :]))
+            xh = z[:, :xd]
+            pred.append(xh)
+            if relift:
+                z = net.x_encoder(xh)
+        return torch.stack(pred, dim=1)
+
+
+def prediction_errors(pred, x, npos=3):
+    """The reference's evaluation metrics (``train.py:79-82`` over ``losses.py:158-172``) of a
+    prediction pred [N, T+1, x_dim] against x: the mean absolute error over trajectories, the T
+    predicted steps and dims -- all of x (``avg_error``), x[:npos] (``dis_error``, the end-effector
+    position) and x[npos:] (``angle_error``, the joint angles).  Floats."""
+    pred = torch.as_tensor(pred)
+    d = (pred[:, 1:, :].double() - torch.as_tensor(x)[:, 1:, :].to(device=pred.device, dtype=torch.float64)).abs()
+    return dict(avg_error=float(d.mean()), dis_error=float(d[:, :, :npos].mean()),
+                angle_error=float(d[:, :, npos:].mean()))
 
 
 _TOEPLITZ = {}
