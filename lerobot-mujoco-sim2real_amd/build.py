@@ -17,7 +17,7 @@ SRC_DIR = os.path.join(PKG_DIR, "csrc")
 SOURCES = ["soarm_sim.hip", "koopman_mpc.hip", "soarm_cpu.hip"]
 # translation units compiled for the host only (the CPU backend: no kernels)
 HOST_ONLY = {"soarm_cpu.hip"}
-HEADERS = ["dmodel.h", "soarm_kernels.h", "soarm_step.h", "soarm_collide.h", "soarm_pgs.h", "soarm_newton.h",
+HEADERS = ["dmodel.h", "soarm_kernels.h", "soarm_step.h", "soarm_collide.h", "soarm_pgs.h", "soarm_rs.h", "soarm_newton.h",
            "soarm_prof.h", "soarm_substep.h",
            "soarm_env.h", "sim_internal.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -8,8 +8,9 @@
 // lower/upper, then contacts in candidate-pair order), so the sweep matches
 // the oracle's.
 //
-// Where the rows live (one lane = one env, one wave per SIMD at 4096 envs, so
-// every sweep is an issue-bound chain and nothing may come from global memory):
+// Where the rows live (4 lanes per env in the contact substep kernel, 16 in its RS
+// variant, one lane per env in the contact-free k_step; one wave per SIMD at 4096 envs,
+// so every sweep is an issue-bound chain and nothing may come from global memory):
 //  * dof-frictionloss rows: registers; J = e_i, W = M^-1 J' is a column of the
 //    arm block's explicit inverse;
 //  * joint-limit rows (rare): a compact list of active rows in LDS;
@@ -43,13 +44,6 @@ constexpr int LDS_CON = 6;  // contacts whose rows stay in LDS
 // contact k's residuals (its cross-Gram row), broadcast within the quad (DPP) on that
 // contact's turn.  The arm-only scene has no block; its quad splits the other parts.
 constexpr int QUAD_LPE = 4;
-// value of lane J of each quad (DPP quad_perm broadcast); J is a compile-time 0..3
-// projected Gauss-Seidel step of a pyramid edge, max(x, -f): one VOP3 max with a
-// negated source.  fmaxf(x, -f) on a loop-carried f costs an extra canonicalising
-// v_max(-f, -f) per edge (IEEE mode: the compiler cannot prove -f canonical); every
-// operand here is a finite arithmetic result, so the plain instruction is exact.
-// Used only in loops without memory reads: an inline asm is not known to return, so
-// LICM keeps loads that follow it inside the loop.
 // packed FP32 (v_pk_fma_f32 / v_pk_add_f32): one wave per SIMD issues a VALU op every
 // ~4.7 cycles whether it is packed or not, so two independent FMAs on a register pair
 // cost one issue slot (tools/mb_chain.hip)
@@ -63,6 +57,12 @@ DEVI f2 fma2_hi(f2 a, f2 b, f2 c) {
   asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
   return r;
 }
+// projected Gauss-Seidel step of a pyramid edge, max(x, -f): one VOP3 max with a
+// negated source.  fmaxf(x, -f) on a loop-carried f costs an extra canonicalising
+// v_max(-f, -f) per edge (IEEE mode: the compiler cannot prove -f canonical); every
+// operand here is a finite arithmetic result, so the plain instruction is exact.
+// Used only in loops without memory reads: an inline asm is not known to return, so
+// LICM keeps loads that follow it inside the loop.
 DEVI float max_neg(float x, float f) {
   float r;
   asm("v_max_f32_e64 %0, %1, -%2" : "=v"(r) : "v"(x), "v"(f));
@@ -71,6 +71,7 @@ DEVI float max_neg(float x, float f) {
 // re-define a value in a VGPR (an empty asm): starts a new live range at this point
 DEVI void vpin(float& x) { asm volatile("" : "+v"(x)); }
 DEVI void vpin(f2& x) { asm volatile("" : "+v"(x)); }
+// value of lane J of each quad (DPP quad_perm broadcast); J is a compile-time 0..3
 DEVI float qbcast(float x, int j) {
   const int b = __float_as_int(x);
   switch (j) {
@@ -108,165 +109,6 @@ constexpr float ARM_RETIRE = 1e-6f;
 constexpr int XS_LIST = SIM_MAXCON;           // ext[0, XS_LIST): the env's contact list (quad build)
 constexpr int XS_EXT = XS_LIST + 98;           // + extra-slot scratch beyond the limit list
 enum { L_DOF = 0, L_SGN = 1, L_AREF = 2, L_R = 3, L_ARD = 4, L_IARD = 5, L_FRC = 6 };
-
-// ---- Row-space PGS (the RS kernel: k_substep<..., RS>, 16 lanes per env, 4 envs per wave).
-// MuJoCo's mj_solPGS sweeps the dual on the dense matrix AR = J M^-1 J' + R (efc_AR): row i's
-// residual is AR_i f + b_i, its force steps by -res / AR_ii and is projected (frictionloss
-// rows into [-fl, fl], limit rows and pyramid edges to f >= 0), rows in order.  The RS kernel
-// holds that system directly: lane r of an env's 16-lane DPP row owns constraint rows r
-// (slot A) and 16 + r (slot B) -- every frictionloss, limit and pyramid-edge row, from the
-// first sweep to the last -- with the row's scaled residual s_r = -res_r / AR_rr and its row of
-// the scaled matrix C[r][q] = -AR_rq / AR_rr (C[r][r] = -1) in registers.  Step q of a sweep:
-// the projected step d = clamp(s_q, lo_q - f_q, hi_q - f_q) is formed from lane q's residual by
-// a DPP row broadcast fused into the max (v_max_f32_dpp row_newbcast), every lane moves its
-// residuals by C[r][q] d (one packed FMA per slot), and the step's bound registers (-f_q,
-// kept broadcast in every lane of the env) take it: two dependent instructions per row.
-// The improvement of mj_solPGS's stopping test is the sweep's exact cost change: with
-// res = AR f + b, cost(f0) - cost(f1) = sum_r AR_rr / 2 (f1 - f0)_r (s0 + s1)_r, and each
-// row's force change over the sweep is its own step, which a second accumulator beside s takes
-// exactly (its coefficient is 1 at the row's own step, 0 elsewhere).
-#ifndef SOARM_RS_SEQ
-#define SOARM_RS_SEQ 0  // 1: the decoupled layouts' steps one at a time (A/B of the paired sweep)
-#endif
-constexpr int RS_MAXROW = 32;               // rows of one env (2 slots x 16 lanes)
-constexpr int RS_WROW = 12;                 // floats per row of W = M^-1 J' in LDS (NV <= 12)
-constexpr int RS_WENV = RS_MAXROW * RS_WROW + 4;  // per env (+4: the 4 envs of a wave on distinct banks)
-constexpr int RS_EPW = 4;                   // envs per wave (workgroup)
-template <int Q>
-DEVI float rowbcast(float x) {  // lane Q of each 16-lane row
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x150 + Q, 0xF, 0xF, true));
-}
-// sum over the 16-lane row, bit-identical in all 16 lanes (the stop test must agree)
-// (the permutes fused into the adds, v_add_f32_dpp; every stage adds two values that are equal
-// bit for bit within each pair of partners -- quad xor 1, quad xor 2, the 8-lane mirror, the
-// 16-lane mirror -- and fp addition is commutative, so all 16 lanes end with the same bits)
-DEVI float rowsum16(float x) {
-  asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "+v"(x));
-  asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "+v"(x));
-  asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf" : "+v"(x));
-  asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf" : "+v"(x));
-  return x;
-}
-// max(lane Q's x, b): the row broadcast fused into the max (VOP2 DPP).  A DPP read of a VGPR needs
-// 2 wait states after the VALU write of it, and the compiler's hazard recognizer does not look into
-// inline asm: the caller states how many instructions (NOPS = 2 - that count) must be padded.
-template <int Q, int NOPS = 2>
-DEVI float max_bcast(float x, float b) {
-  float r;
-  if constexpr (NOPS >= 2)
-    asm volatile("s_nop 1\n\tv_max_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x), "v"(b), "i"(Q));
-  else if constexpr (NOPS == 1)
-    asm volatile("s_nop 0\n\tv_max_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x), "v"(b), "i"(Q));
-  else
-    asm volatile("v_max_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x), "v"(b), "i"(Q));
-  return r;
-}
-DEVI float vmin(float a, float b) {  // v_min without the IEEE-mode canonicalising of fminf
-  float r;
-  asm("v_min_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-// f(std::integral_constant<int, i>) for i = 0 .. N-1 (compile-time lane / register indices)
-template <class F, int... Is>
-DEVI void sfor_impl(F&& f, std::integer_sequence<int, Is...>) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-DEVI void sfor(F&& f) {
-  sfor_impl(f, std::make_integer_sequence<int, N>{});
-}
-// Row layout of one wave's RS solve (compile time).  Steps in mj_solPGS order: the NA dof
-// frictionloss rows (F), then the edges of up to KAT arm-only contacts (AT: arm on the table /
-// floor, arm self-contacts), of up to 4 contacts on the free body alone (CT: the cube on the
-// table), of up to KAC contacts between the arm and the free body (AC) -- the order the pair
-// list produces (arm-only pairs precede the free body's, its world pairs precede its arm pairs).
-// Rows touching arm dofs (F, AT, AC) live in slot B, the CT edges in slot A: M is block diagonal,
-// so an F / AT step moves slot B alone and a CT step slot A alone (and slot B's AC rows when the
-// wave has an AC contact); a step therefore costs one residual update where the systems decouple.
-// Steps an env has no row for are zero rows (exact no-ops).
-template <int NA, int KAT, int KAC>
-struct RsLayout {
-  static_assert(NA + 4 * (KAT + KAC) <= 16, "slot B holds the F, AT and AC rows");
-  static constexpr int CT0 = NA + 4 * KAT, AC0 = CT0 + 16, NS = AC0 + 4 * KAC;
-  static constexpr bool decoupled = KAC == 0;  // no AC rows: the slot-B (arm) and slot-A (cube) steps never meet
-  static constexpr int slot(int q) { return (q >= CT0 && q < AC0) ? 0 : 1; }
-  static constexpr int lane(int q) { return q < CT0 ? q : q < AC0 ? q - CT0 : q - 16; }
-  static constexpr bool upd_a(int q) { return q >= CT0; }                 // CT, AC
-  static constexpr bool upd_b(int q) { return q < CT0 || q >= AC0 || KAC > 0; }
-  // instructions after step q's write of slot sl before step q+1 (see rs_sweep's order)
-  static constexpr int after_write(int q, int sl) {
-    return (sl == 0 ? upd_a(q) : upd_b(q)) ? ((upd_a(q) && upd_b(q)) ? 1 : 0) + 1 + (q < NA ? 1 : 0) : 2;
-  }
-};
-// one sweep of the row-space PGS (see above): s = (residual, own-step accumulator) per slot,
-// C = (C, G) pairs per step, NF = lo - f of every row, NH = hi - f of the NA frictionloss rows (the
-// others have hi = +inf).  Instruction order is pinned (sched_barrier): a DPP op waits for every
-// VALU op in flight, so a step is its broadcast-max, the residual update of the slot the NEXT step
-// broadcasts from, then the other slot's update and the bound updates -- which are also the 2 wait
-// states the next broadcast needs after that write (padded with s_nop where a step has fewer)
-//
-// Layouts without AC rows (KAC = 0: no arm-cube contact in the wave, ~99.6% of the headline's waves)
-// are two systems that never meet: the F / AT steps read and move slot B alone, the CT steps slot A
-// alone (M is block diagonal).  Their steps then run paired -- B step i beside A step i, two
-// independent chains in one instruction stream, each hiding the other's latency and DPP drain --
-// and each slot still takes its own steps in mj_solPGS order, so every residual, force and
-// accumulator is bit-identical to the sequential sweep.
-template <int NA, class LY>
-DEVI void rs_sweep(f2& sA, f2& sB, const f2 (&CA)[LY::NS], const f2 (&CB)[LY::NS], float (&NF)[LY::NS],
-                   float (&NH)[NA]) {
-  if constexpr (LY::decoupled && !SOARM_RS_SEQ) {
-    constexpr int NB = LY::CT0, NAS = LY::NS - LY::CT0;  // slot-B steps (F, AT), slot-A steps (CT)
-    static_assert(NB <= NAS, "slot A has at least as many steps as slot B");
-    sfor<NAS>([&](auto ic) {
-      constexpr int I = decltype(ic)::value;
-      constexpr bool HB = I < NB;
-      constexpr int QA = LY::CT0 + I;
-      // wait states before this step's broadcasts (2 needed after the VALU write of the source):
-      // B reads sB, written by step I-1's first update, with the sA update and >= 2 bound updates
-      // after it; A reads sA, written by step I-1's second update, with step I-1's bound updates
-      // (2 when it had a B step, else 1) and this step's B broadcast after it
-      constexpr int waitA = I == 0 ? 0 : ((I - 1) < NB ? 2 + (HB ? 1 : 0) : 1 + (HB ? 1 : 0));
-      float dB = 0.f, dA;
-      if constexpr (HB) dB = max_bcast<LY::lane(I), (I == 0 ? 2 : 0)>(sB.x, NF[I]);
-      dA = max_bcast<LY::lane(QA), (waitA >= 2 ? 0 : 2 - waitA)>(sA.x, NF[QA]);
-      if constexpr (HB && I < NA) dB = vmin(dB, NH[I]);
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (HB) sB = __builtin_elementwise_fma(CB[I], f2{dB, dB}, sB);
-      __builtin_amdgcn_sched_barrier(0);
-      sA = __builtin_elementwise_fma(CA[QA], f2{dA, dA}, sA);
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (HB) {
-        NF[I] -= dB;
-        if constexpr (I < NA) NH[I] -= dB;
-      }
-      NF[QA] -= dA;
-      __builtin_amdgcn_sched_barrier(0);
-    });
-    return;
-  }
-  sfor<LY::NS>([&](auto qc) {
-    constexpr int Q = decltype(qc)::value;
-    constexpr int SL = LY::slot(Q), LN = LY::lane(Q);
-    constexpr int after = Q == 0 ? 0 : LY::after_write(Q - 1, SL);
-    float d = max_bcast<LN, (after >= 2 ? 0 : 2 - after)>(SL == 0 ? sA.x : sB.x, NF[Q]);
-    if constexpr (Q < NA) d = vmin(d, NH[Q]);
-    __builtin_amdgcn_sched_barrier(0);
-    constexpr int NSL = Q + 1 < LY::NS ? LY::slot(Q + 1) : SL;  // the next step's source slot
-    auto upd = [&](auto slc) {
-      if constexpr (decltype(slc)::value == 0) {
-        if constexpr (LY::upd_a(Q)) sA = __builtin_elementwise_fma(CA[Q], f2{d, d}, sA);
-      } else {
-        if constexpr (LY::upd_b(Q)) sB = __builtin_elementwise_fma(CB[Q], f2{d, d}, sB);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    upd(std::integral_constant<int, NSL>{});
-    upd(std::integral_constant<int, 1 - NSL>{});
-    NF[Q] -= d;
-    if constexpr (Q < NA) NH[Q] -= d;
-    __builtin_amdgcn_sched_barrier(0);
-  });
-}
 
 // Per-env LDS state, [field][column]: one column per env of the workgroup (64 / lanes per
 // env); the lanes of an env share its column (identical values, or records written by the
@@ -482,12 +324,349 @@ DEVI void gram_step(float* v6, const float* jn, const float* j1, const float* j2
 
 }  // namespace soarm
 #include "soarm_newton.h"
+#include "soarm_rs.h"
 namespace soarm {
+
+// contacts of the register block (the free-body contact scene; see solve_constraints)
+template <int NF, bool CON>
+constexpr int BLOCK_FC = (NF == 1 && CON) ? 4 : 1;
+
+// The v-form sweeps: PGS on the velocity v = qacc_smooth + M^-1 J' f, row by row in mj_solPGS order
+// (frictionloss rows, active limits, contacts from their LDS records or the overflow slab), with the
+// register block of the free-body scene beside the frictionloss rows (first: the block commutes with
+// every row before it).  Every scene's fallback, and the only solver of the scenes without a free
+// body.  Reads the rows' constants and the counts solve_constraints made; writes v, ff, the block's
+// forces cfo and the forces in the limit / contact records.
+template <bool CON, int NA, int NF, class FI>
+DEVI void vsweeps(FI first, const DModel& m, const RowLds& L, const ContactRows<NA, NF>& cr, const MInv<NA, NF>& Mi,
+                  float (&v)[NA + 6 * NF], float (&ff)[NA], const float (&fa)[NA], const float (&fR)[NA],
+                  const float (&fhD)[NA], const float (&fiD)[NA], float (&cfo)[BLOCK_FC<NF, CON>][4],
+                  const float (&ccf)[BLOCK_FC<NF, CON>][12], const int (&cslot)[BLOCK_FC<NF, CON>], const int nlim,
+                  const int nl, const int ncon, const int npre, const int npost, const int c0, const int c1,
+                  const float scale PROF_DECL(, int& nsweep)) {
+  constexpr int NV = NA + 6 * NF, FC = BLOCK_FC<NF, CON>;
+  // dof-frictionloss rows (J = e_i): one pass.  Branch-free: a dof with frictionloss 0
+  // (no row in MuJoCo) clamps to [0, 0] and stays an exact no-op.
+  auto fric_rows = [&](float& improvement) {
+#pragma unroll
+    for (int i = 0; i < NA; i++) {
+      const float fl = m.dof_frictionloss[i];
+      const float res = v[i] - fa[i] + fR[i] * ff[i];
+      const float fn = fminf(fmaxf(ff[i] - res * fiD[i], -fl), fl);
+      const float df = fn - ff[i];
+#pragma unroll
+      for (int k = 0; k < NA; k++) v[k] += Mi.a(i, k) * df;
+      ff[i] = fn;
+      improvement -= df * (res + fhD[i] * df);
+    }
+  };
+  // active joint-limit rows (LDS list; usually empty)
+  auto limit_rows = [&](float& improvement) {
+    for (int l = 0; l < nlim; l++) {
+      float oh[NA];
+      one_hot<NA>((int)L.lm(l, L_DOF), oh);
+      const float sg = L.lm(l, L_SGN), fo = L.lm(l, L_FRC);
+      const float res = sg * pick<NA>(v, oh) - L.lm(l, L_AREF) + L.lm(l, L_R) * fo;
+      const float fn = fmaxf(fo - res * L.lm(l, L_IARD), 0.f);
+      const float df = fn - fo;
+      add_arm_col(Mi, v, oh, sg * df);
+      L.lm(l, L_FRC) = fn;
+      improvement -= df * (res + 0.5f * L.lm(l, L_ARD) * df);
+    }
+  };
+  // arm-only contact c: NA-dof dots, the 4-edge chain, one arm-block M^-1 product
+  auto arm_v = [&](int c, float mu, float Rp, const float* cf, float* fo, const float* ar, const float* ia,
+                   const float* hd, float& improvement) {
+    float jn[NA], j1[NA], j2[NA];
+#pragma unroll
+    for (int i = 0; i < NA; i++) jn[i] = L.at(c, i), j1[i] = L.at(c, 12 + i), j2[i] = L.at(c, 24 + i);
+    float a = 0.f, b = 0.f, cc = 0.f;
+#pragma unroll
+    for (int i = 0; i < NA; i++) a += jn[i] * v[i], b += j1[i] * v[i], cc += j2[i] * v[i];
+    float df[4];
+#pragma unroll
+    for (int ed = 0; ed < 4; ed++) {
+      const float s = (ed & 1) ? -mu : mu;
+      const float res = (a + s * ((ed >> 1) ? cc : b)) - ar[ed] + Rp * fo[ed];
+      const float fnew = fmaxf(fo[ed] - res * ia[ed], 0.f);
+      df[ed] = fnew - fo[ed];
+      a += cf[3 * ed] * df[ed];
+      b += cf[3 * ed + 1] * df[ed];
+      cc += cf[3 * ed + 2] * df[ed];
+      improvement -= df[ed] * (res + hd[ed] * df[ed]);
+      fo[ed] = fnew;
+    }
+    const float Dn = (df[0] + df[1]) + (df[2] + df[3]);
+    const float D1 = mu * (df[0] - df[1]), D2 = mu * (df[2] - df[3]);
+    float u[NA];
+#pragma unroll
+    for (int i = 0; i < NA; i++) u[i] = jn[i] * Dn + j1[i] * D1 + j2[i] * D2;
+#pragma unroll
+    for (int i = 0; i < NA; i++) {
+      float w = 0.f;
+#pragma unroll
+      for (int k = 0; k < NA; k++) w += Mi.a(i, k) * u[k];
+      v[i] += w;
+    }
+#pragma unroll
+    for (int ed = 0; ed < 4; ed++) L.at(c, F_FRC + ed) = fo[ed];
+  };
+  // contact c from its LDS record, in Gram form: a 6-dof free-body update when
+  // (wave-uniformly) it touches only the free body, otherwise full-width dots and one
+  // M^-1 product per sweep for the velocity update
+  auto lds_contact = [&](int c, float& improvement) {
+    const bool ta = (int)L.at(c, F_FLAGS) & TOUCH_ARM;
+    float G[6], cf[12], fo[4], ar[4], ia[4], hd[4];
+#pragma unroll
+    for (int ed = 0; ed < 4; ed++)
+      fo[ed] = L.at(c, F_FRC + ed), ar[ed] = L.at(c, F_AREF + ed), ia[ed] = L.at(c, F_IARD + ed),
+      hd[ed] = L.at(c, F_HARD + ed);
+#pragma unroll
+    for (int k = 0; k < 6; k++) G[k] = L.at(c, F_GRAM + k);
+    const float mu = L.at(c, F_MU), Rp = L.at(c, F_R);
+    gram_coefs(G, mu, cf);
+    if constexpr (NF == 1) {
+      if (__all(!ta)) {
+        float jn[6], j1[6], j2[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+          jn[i] = L.at(c, NA + i), j1[i] = L.at(c, 12 + NA + i), j2[i] = L.at(c, 24 + NA + i);
+        gram_step(v + NA, jn, j1, j2, cf, ar, ia, hd, fo, mu, Rp, Mi.Fd[0], improvement);
+#pragma unroll
+        for (int ed = 0; ed < 4; ed++) L.at(c, F_FRC + ed) = fo[ed];
+        return;
+      }
+    }
+    if (__all(!((int)L.at(c, F_FLAGS) & TOUCH_FREE))) {
+      // arm-only contact (link vs table / floor / link): NA-dof dots, one arm-block
+      // M^-1 product per sweep
+      arm_v(c, mu, Rp, cf, fo, ar, ia, hd, improvement);
+      return;
+    }
+    // the record holds zeros in the halves the contact does not touch: full-width,
+    // branch-free dots (divergent half-selection would run both sides anyway)
+    float jn[NV], j1[NV], j2[NV];
+#pragma unroll
+    for (int i = 0; i < NV; i++) jn[i] = L.at(c, i), j1[i] = L.at(c, 12 + i), j2[i] = L.at(c, 24 + i);
+    float a = 0.f, b = 0.f, cc = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; i++) a += jn[i] * v[i], b += j1[i] * v[i], cc += j2[i] * v[i];
+    float df[4];
+#pragma unroll
+    for (int ed = 0; ed < 4; ed++) {
+      const float s = (ed & 1) ? -mu : mu;
+      const float res = (a + s * ((ed >> 1) ? cc : b)) - ar[ed] + Rp * fo[ed];
+      const float fnew = fmaxf(fo[ed] - res * ia[ed], 0.f);
+      df[ed] = fnew - fo[ed];
+      a += cf[3 * ed] * df[ed];
+      b += cf[3 * ed + 1] * df[ed];
+      cc += cf[3 * ed + 2] * df[ed];
+      improvement -= df[ed] * (res + hd[ed] * df[ed]);
+      fo[ed] = fnew;
+    }
+    const float Dn = (df[0] + df[1]) + (df[2] + df[3]);
+    const float D1 = mu * (df[0] - df[1]), D2 = mu * (df[2] - df[3]);
+    float u[NV], w[NV];
+#pragma unroll
+    for (int i = 0; i < NV; i++) u[i] = jn[i] * Dn + j1[i] * D1 + j2[i] * D2;
+    Mi.mul(u, w, true, true);
+#pragma unroll
+    for (int i = 0; i < NV; i++) v[i] += w[i];
+#pragma unroll
+    for (int ed = 0; ed < 4; ed++) L.at(c, F_FRC + ed) = fo[ed];
+  };
+  // contacts beyond LDS_CON: per-edge J/W rows in global scratch (rare)
+  auto scratch_rows = [&](float& improvement) {
+    for (int r = 4 * nl; r < 4 * ncon; r++) {
+      float res = -cr.S(r, 0) + cr.S(r, 1) * cr.S(r, 3);
+#pragma unroll
+      for (int i = 0; i < NV; i++) res += cr.J(r, i) * v[i];
+      const float fo = cr.S(r, 3);
+      const float fnew = fmaxf(fo - res / cr.S(r, 2), 0.f);
+      const float df = fnew - fo;
+      if (df != 0.f) {
+#pragma unroll
+        for (int i = 0; i < NV; i++) v[i] += cr.W(r, i) * df;
+        cr.S(r, 3) = fnew;
+        improvement -= df * res + 0.5f * cr.S(r, 2) * df * df;
+      }
+    }
+  };
+  // the block's sweep (straight-line: one basic block with the friction rows)
+  auto block_rows = [&](float& improvement) {
+    if constexpr (NF == 1 && CON) {
+#pragma unroll
+      for (int k = 0; k < FC; k++) {
+        const int c = cslot[k];
+        float jn[6], j1[6], j2[6], ar[4], ia[4], hd[4];
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+          jn[i] = L.at(c, NA + i), j1[i] = L.at(c, 12 + NA + i), j2[i] = L.at(c, 24 + NA + i);
+#pragma unroll
+        for (int ed = 0; ed < 4; ed++)
+          ar[ed] = L.at(c, F_AREF + ed), ia[ed] = L.at(c, F_IARD + ed), hd[ed] = L.at(c, F_HARD + ed);
+        const float mu = L.at(c, F_MU), Rp = L.at(c, F_R);
+        gram_step(v + NA, jn, j1, j2, ccf[k], ar, ia, hd, cfo[k], mu, Rp, Mi.Fd[0], improvement);
+      }
+    }
+  };
+  for (int it = 0; it < m.iterations; it++) {
+    float improvement = 0.f;
+    if constexpr (decltype(first)::value) {
+      fric_rows(improvement);  // same basic block as the register block: they interleave
+      block_rows(improvement);
+      limit_rows(improvement);
+      for (int j = 0; j < npost; j++) lds_contact(j < c0 - npre ? npre + j : c1 + j - (c0 - npre), improvement);
+      scratch_rows(improvement);
+    } else {
+      fric_rows(improvement);
+      limit_rows(improvement);
+      for (int c = 0; c < npre; c++) lds_contact(c, improvement);
+      block_rows(improvement);
+      for (int j = 0; j < npost; j++) lds_contact(j < c0 - npre ? npre + j : c1 + j - (c0 - npre), improvement);
+      scratch_rows(improvement);
+    }
+    if (improvement * scale < m.tolerance) {
+      PROF_DO(nsweep = it + 1);
+      break;
+    }
+  }
+}
+
+// After the solve: qacc = v and qfrc_constraint = J' f (the forces are in ff and the limit / contact
+// records by now).
+template <bool CON, bool RS, int NA, int NF>
+DEVI void write_qacc_fcon(Sim<NA, NF>& S, const RowLds& L, const ContactRows<NA, NF>& cr, const float (&v)[NA + 6 * NF],
+                          const float (&ff)[NA], const int nlim, const int nl, const int ncon) {
+  constexpr int NV = NA + 6 * NF;
+#pragma unroll
+  for (int i = 0; i < NV; i++) {
+    S.qacc[i] = v[i];
+    S.fcon[i] = 0.f;
+  }
+  if constexpr (CON && RS) return;  // (the RS kernel's Euler step needs qacc alone: integrate_qacc)
+  if constexpr (CON) {
+    // qacc = qacc_smooth + M^-1 J' f, so J' f = M qacc - qfrc_smooth (M qacc_smooth = qfrc_smooth):
+    // the Euler step's right-hand side qfrc_smooth + qfrc_constraint is M qacc.  One 6x6 product
+    // (+ the free bodies' diagonal blocks) instead of J' f over every contact row; equal in exact
+    // arithmetic, fp32 rounding apart (the oracle keeps J' f).
+#pragma unroll
+    for (int i = 0; i < NA; i++) {
+      float sacc = -S.fsmooth[i];
+#pragma unroll
+      for (int k = 0; k < NA; k++) sacc = fmaf(S.MA[i >= k ? i * (i + 1) / 2 + k : k * (k + 1) / 2 + i], v[k], sacc);
+      S.fcon[i] = sacc;
+    }
+#pragma unroll
+    for (int f = 0; f < NF; f++)
+#pragma unroll
+      for (int i = 0; i < 6; i++) {
+        const int d = NA + 6 * f + i;
+        S.fcon[d] = fmaf(S.MF[f][i * (i + 1) / 2 + i], v[d], -S.fsmooth[d]);
+      }
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < NA; i++) S.fcon[i] += ff[i];
+  for (int l = 0; l < nlim; l++) {
+    float oh[NA];
+    one_hot<NA>((int)L.lm(l, L_DOF), oh);
+    const float t = L.lm(l, L_SGN) * L.lm(l, L_FRC);
+#pragma unroll
+    for (int k = 0; k < NA; k++) S.fcon[k] = fmaf(oh[k], t, S.fcon[k]);
+  }
+  for (int c = 0; c < nl; c++) {
+    float jn[NV], jt1[NV], jt2[NV];
+#pragma unroll
+    for (int i = 0; i < NV; i++) jn[i] = L.at(c, i), jt1[i] = L.at(c, 12 + i), jt2[i] = L.at(c, 24 + i);
+    const float mu = L.at(c, F_MU);
+#pragma unroll
+    for (int ed = 0; ed < 4; ed++) {
+      float J[NV];
+      edge_J<NV>(jn, jt1, jt2, ed, mu, J);
+      const float fr = L.at(c, F_FRC + ed);
+#pragma unroll
+      for (int i = 0; i < NV; i++) S.fcon[i] += J[i] * fr;
+    }
+  }
+  for (int r = 4 * nl; r < 4 * ncon; r++) {
+    const float fr = cr.S(r, 3);
+#pragma unroll
+    for (int i = 0; i < NV; i++) S.fcon[i] += cr.J(r, i) * fr;
+  }
+}
+
+// The state that only the stages after the solve need -- mass matrix blocks, smooth forces, the observed
+// site; in the RS kernel the damped Euler step's factor (Sim::damp_factor) instead -- waits in LDS
+// (RowLds::keep) while the sweeps run, so the sweeps' register budget is not spent holding it.
+// park_kept before the sweeps, restore_kept after them: one layout, read back in the order written.
+template <bool RS, int NA, int NF>
+DEVI void park_kept(Sim<NA, NF>& S, const RowLds& L) {
+  constexpr int NV = NA + 6 * NF;
+  if constexpr (RS) {  // the RS kernel: the damped Euler step's factor instead (Sim::damp_factor)
+    S.damp_factor();
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < NA * (NA + 1) / 2; i++) L.kp(k++) = S.LH[i];
+#pragma unroll
+    for (int i = 0; i < NA; i++) L.kp(k++) = S.DHi[i];
+#pragma unroll
+    for (int i = 0; i < 6 * NF; i++) L.kp(k++) = S.kf[i / 6][i % 6];
+#pragma unroll
+    for (int i = 0; i < 3; i++) L.kp(k++) = S.ee[i];
+  } else if (L.keep) {  // park what only the post-solve stages need (restored below)
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < NA * (NA + 1) / 2; i++) L.kp(k++) = S.MA[i];
+#pragma unroll
+    for (int f2 = 0; f2 < NF; f2++)
+#pragma unroll
+      for (int i = 0; i < 6; i++) L.kp(k++) = S.MF[f2][i * (i + 1) / 2 + i];
+#pragma unroll
+    for (int i = 0; i < NV; i++) L.kp(k++) = S.fsmooth[i];
+#pragma unroll
+    for (int i = 0; i < 3; i++) L.kp(k++) = S.ee[i];
+  }
+}
+
+template <bool RS, int NA, int NF>
+DEVI void restore_kept(Sim<NA, NF>& S, const RowLds& L) {
+  constexpr int NV = NA + 6 * NF;
+  if constexpr (RS) {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < NA * (NA + 1) / 2; i++) S.LH[i] = L.kp(k++);
+#pragma unroll
+    for (int i = 0; i < NA; i++) S.DHi[i] = L.kp(k++);
+#pragma unroll
+    for (int i = 0; i < 6 * NF; i++) S.kf[i / 6][i % 6] = L.kp(k++);
+#pragma unroll
+    for (int i = 0; i < 3; i++) S.ee[i] = L.kp(k++);
+  } else if (L.keep) {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < NA * (NA + 1) / 2; i++) S.MA[i] = L.kp(k++);
+#pragma unroll
+    for (int f2 = 0; f2 < NF; f2++)
+#pragma unroll
+      for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = 0; j <= i; j++) S.MF[f2][i * (i + 1) / 2 + j] = (i == j) ? L.kp(k++) : 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; i++) S.fsmooth[i] = L.kp(k++);
+#pragma unroll
+    for (int i = 0; i < 3; i++) S.ee[i] = L.kp(k++);
+  }
+}
 
 // Builds every constraint row, solves the dual by PGS (or, SOL = Newton, the primal by
 // soarm_newton.h), sets S.qacc / S.fcon.
 // Contacts are read straight from the collide output (pair mask + cbuf, pair
 // order).  Returns the number of contacts used.
+// Stages, in order: the rows (frictionloss, limits, contacts with the RS vote), the Newton hand-off,
+// the warm start, park_kept, the register block's setup, one of three solvers -- vsweeps (above),
+// the y-form block sweeps (still lambdas of this function: DESIGN.md section 0 has the figures of the
+// shapes that were tried), rs_solve (soarm_rs.h) -- then restore_kept and write_qacc_fcon.
 template <int NA, int NF, bool CON, int SOL = SIM_SOL_PGS, bool RS = false>
 DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const int* __restrict__ ccount,
                            const uint32_t* __restrict__ pmask, int n, int e, const RowLds& L,
@@ -913,188 +1092,17 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
   // ---- projected Gauss-Seidel sweeps (mj_solPGS's improvement criterion, scaled by the model
   // constant 1 / (meaninertia * max(1, nv)), meaninertia = trace(M(qpos0)) / nv)
   const float scale = m.pgs_scale;
-  if constexpr (RS) {  // the RS kernel: the damped Euler step's factor instead (Sim::damp_factor)
-    S.damp_factor();
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < NA * (NA + 1) / 2; i++) L.kp(k++) = S.LH[i];
-#pragma unroll
-    for (int i = 0; i < NA; i++) L.kp(k++) = S.DHi[i];
-#pragma unroll
-    for (int i = 0; i < 6 * NF; i++) L.kp(k++) = S.kf[i / 6][i % 6];
-#pragma unroll
-    for (int i = 0; i < 3; i++) L.kp(k++) = S.ee[i];
-  } else if (L.keep) {  // park what only the post-solve stages need (restored below)
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < NA * (NA + 1) / 2; i++) L.kp(k++) = S.MA[i];
-#pragma unroll
-    for (int f2 = 0; f2 < NF; f2++)
-#pragma unroll
-      for (int i = 0; i < 6; i++) L.kp(k++) = S.MF[f2][i * (i + 1) / 2 + i];
-#pragma unroll
-    for (int i = 0; i < NV; i++) L.kp(k++) = S.fsmooth[i];
-#pragma unroll
-    for (int i = 0; i < 3; i++) L.kp(k++) = S.ee[i];
-  }
+  park_kept<RS>(S, L);
   PROF_DO(if (e < 65536) g_pgs_prof[8 * e] = clock64());
   PSTAMP(9);
   PROF_DECL(int nsweep = m.iterations, armstop = 0);
-  // dof-frictionloss rows (J = e_i): one pass.  Branch-free: a dof with frictionloss 0
-  // (no row in MuJoCo) clamps to [0, 0] and stays an exact no-op.
-  auto fric_rows = [&](float& improvement) {
-#pragma unroll
-    for (int i = 0; i < NA; i++) {
-      const float fl = m.dof_frictionloss[i];
-      const float res = v[i] - fa[i] + fR[i] * ff[i];
-      const float fn = fminf(fmaxf(ff[i] - res * fiD[i], -fl), fl);
-      const float df = fn - ff[i];
-#pragma unroll
-      for (int k = 0; k < NA; k++) v[k] += Mi.a(i, k) * df;
-      ff[i] = fn;
-      improvement -= df * (res + fhD[i] * df);
-    }
-  };
-  // active joint-limit rows (LDS list; usually empty)
-  auto limit_rows = [&](float& improvement) {
-    for (int l = 0; l < nlim; l++) {
-      float oh[NA];
-      one_hot<NA>((int)L.lm(l, L_DOF), oh);
-      const float sg = L.lm(l, L_SGN), fo = L.lm(l, L_FRC);
-      const float res = sg * pick<NA>(v, oh) - L.lm(l, L_AREF) + L.lm(l, L_R) * fo;
-      const float fn = fmaxf(fo - res * L.lm(l, L_IARD), 0.f);
-      const float df = fn - fo;
-      add_arm_col(Mi, v, oh, sg * df);
-      L.lm(l, L_FRC) = fn;
-      improvement -= df * (res + 0.5f * L.lm(l, L_ARD) * df);
-    }
-  };
-  // arm-only contact c: NA-dof dots, the 4-edge chain, one arm-block M^-1 product
-  auto arm_v = [&](int c, float mu, float Rp, const float* cf, float* fo, const float* ar, const float* ia,
-                   const float* hd, float& improvement) {
-    float jn[NA], j1[NA], j2[NA];
-#pragma unroll
-    for (int i = 0; i < NA; i++) jn[i] = L.at(c, i), j1[i] = L.at(c, 12 + i), j2[i] = L.at(c, 24 + i);
-    float a = 0.f, b = 0.f, cc = 0.f;
-#pragma unroll
-    for (int i = 0; i < NA; i++) a += jn[i] * v[i], b += j1[i] * v[i], cc += j2[i] * v[i];
-    float df[4];
-#pragma unroll
-    for (int ed = 0; ed < 4; ed++) {
-      const float s = (ed & 1) ? -mu : mu;
-      const float res = (a + s * ((ed >> 1) ? cc : b)) - ar[ed] + Rp * fo[ed];
-      const float fnew = fmaxf(fo[ed] - res * ia[ed], 0.f);
-      df[ed] = fnew - fo[ed];
-      a += cf[3 * ed] * df[ed];
-      b += cf[3 * ed + 1] * df[ed];
-      cc += cf[3 * ed + 2] * df[ed];
-      improvement -= df[ed] * (res + hd[ed] * df[ed]);
-      fo[ed] = fnew;
-    }
-    const float Dn = (df[0] + df[1]) + (df[2] + df[3]);
-    const float D1 = mu * (df[0] - df[1]), D2 = mu * (df[2] - df[3]);
-    float u[NA];
-#pragma unroll
-    for (int i = 0; i < NA; i++) u[i] = jn[i] * Dn + j1[i] * D1 + j2[i] * D2;
-#pragma unroll
-    for (int i = 0; i < NA; i++) {
-      float w = 0.f;
-#pragma unroll
-      for (int k = 0; k < NA; k++) w += Mi.a(i, k) * u[k];
-      v[i] += w;
-    }
-#pragma unroll
-    for (int ed = 0; ed < 4; ed++) L.at(c, F_FRC + ed) = fo[ed];
-  };
-  // contact c from its LDS record, in Gram form: a 6-dof free-body update when
-  // (wave-uniformly) it touches only the free body, otherwise full-width dots and one
-  // M^-1 product per sweep for the velocity update
-  auto lds_contact = [&](int c, float& improvement) {
-    const bool ta = (int)L.at(c, F_FLAGS) & TOUCH_ARM;
-    float G[6], cf[12], fo[4], ar[4], ia[4], hd[4];
-#pragma unroll
-    for (int ed = 0; ed < 4; ed++)
-      fo[ed] = L.at(c, F_FRC + ed), ar[ed] = L.at(c, F_AREF + ed), ia[ed] = L.at(c, F_IARD + ed),
-      hd[ed] = L.at(c, F_HARD + ed);
-#pragma unroll
-    for (int k = 0; k < 6; k++) G[k] = L.at(c, F_GRAM + k);
-    const float mu = L.at(c, F_MU), Rp = L.at(c, F_R);
-    gram_coefs(G, mu, cf);
-    if constexpr (NF == 1) {
-      if (__all(!ta)) {
-        float jn[6], j1[6], j2[6];
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-          jn[i] = L.at(c, NA + i), j1[i] = L.at(c, 12 + NA + i), j2[i] = L.at(c, 24 + NA + i);
-        gram_step(v + NA, jn, j1, j2, cf, ar, ia, hd, fo, mu, Rp, Mi.Fd[0], improvement);
-#pragma unroll
-        for (int ed = 0; ed < 4; ed++) L.at(c, F_FRC + ed) = fo[ed];
-        return;
-      }
-    }
-    if (__all(!((int)L.at(c, F_FLAGS) & TOUCH_FREE))) {
-      // arm-only contact (link vs table / floor / link): NA-dof dots, one arm-block
-      // M^-1 product per sweep
-      arm_v(c, mu, Rp, cf, fo, ar, ia, hd, improvement);
-      return;
-    }
-    // the record holds zeros in the halves the contact does not touch: full-width,
-    // branch-free dots (divergent half-selection would run both sides anyway)
-    float jn[NV], j1[NV], j2[NV];
-#pragma unroll
-    for (int i = 0; i < NV; i++) jn[i] = L.at(c, i), j1[i] = L.at(c, 12 + i), j2[i] = L.at(c, 24 + i);
-    float a = 0.f, b = 0.f, cc = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; i++) a += jn[i] * v[i], b += j1[i] * v[i], cc += j2[i] * v[i];
-    float df[4];
-#pragma unroll
-    for (int ed = 0; ed < 4; ed++) {
-      const float s = (ed & 1) ? -mu : mu;
-      const float res = (a + s * ((ed >> 1) ? cc : b)) - ar[ed] + Rp * fo[ed];
-      const float fnew = fmaxf(fo[ed] - res * ia[ed], 0.f);
-      df[ed] = fnew - fo[ed];
-      a += cf[3 * ed] * df[ed];
-      b += cf[3 * ed + 1] * df[ed];
-      cc += cf[3 * ed + 2] * df[ed];
-      improvement -= df[ed] * (res + hd[ed] * df[ed]);
-      fo[ed] = fnew;
-    }
-    const float Dn = (df[0] + df[1]) + (df[2] + df[3]);
-    const float D1 = mu * (df[0] - df[1]), D2 = mu * (df[2] - df[3]);
-    float u[NV], w[NV];
-#pragma unroll
-    for (int i = 0; i < NV; i++) u[i] = jn[i] * Dn + j1[i] * D1 + j2[i] * D2;
-    Mi.mul(u, w, true, true);
-#pragma unroll
-    for (int i = 0; i < NV; i++) v[i] += w[i];
-#pragma unroll
-    for (int ed = 0; ed < 4; ed++) L.at(c, F_FRC + ed) = fo[ed];
-  };
-  // contacts beyond LDS_CON: per-edge J/W rows in global scratch (rare)
-  auto scratch_rows = [&](float& improvement) {
-    for (int r = 4 * nl; r < 4 * ncon; r++) {
-      float res = -cr.S(r, 0) + cr.S(r, 1) * cr.S(r, 3);
-#pragma unroll
-      for (int i = 0; i < NV; i++) res += cr.J(r, i) * v[i];
-      const float fo = cr.S(r, 3);
-      const float fnew = fmaxf(fo - res / cr.S(r, 2), 0.f);
-      const float df = fnew - fo;
-      if (df != 0.f) {
-#pragma unroll
-        for (int i = 0; i < NV; i++) v[i] += cr.W(r, i) * df;
-        cr.S(r, 3) = fnew;
-        improvement -= df * res + 0.5f * cr.S(r, 2) * df * df;
-      }
-    }
-  };
-
   // Register block: the first run of up to FC consecutive contacts that touch only
   // the free body (the cube's box-box contacts with the table) keeps all its row data
   // in registers for the whole solve, so the common sweep is straight-line code in
   // which the arm's friction chain and the cube's contact chain (independent: M is
   // block diagonal) interleave.  Contacts before / after the run go through their
   // LDS records in row order.  Slots beyond the run are zero rows (1/ARdiag = 0).
-  constexpr int FC = (NF == 1 && CON) ? 4 : 1;
+  constexpr int FC = BLOCK_FC<NF, CON>;
   int c0 = nl, nrun = 0;
   if constexpr (NF == 1 && CON) {
     for (int c = 0; c < nl; c++)
@@ -1140,24 +1148,6 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
   PROF_DECL(int nfree_x = 0);
   PROF_DO(for (int c = 0; c < nl; c++)
             if ((c < c0 || c >= c1) && ((int)L.at(c, F_FLAGS) & TOUCH_FREE)) npost_free = true, nfree_x++);
-  // the block's sweep (straight-line: one basic block with the friction rows)
-  auto block_rows = [&](float& improvement) {
-    if constexpr (NF == 1 && CON) {
-#pragma unroll
-      for (int k = 0; k < FC; k++) {
-        const int c = cslot[k];
-        float jn[6], j1[6], j2[6], ar[4], ia[4], hd[4];
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-          jn[i] = L.at(c, NA + i), j1[i] = L.at(c, 12 + NA + i), j2[i] = L.at(c, 24 + NA + i);
-#pragma unroll
-        for (int ed = 0; ed < 4; ed++)
-          ar[ed] = L.at(c, F_AREF + ed), ia[ed] = L.at(c, F_IARD + ed), hd[ed] = L.at(c, F_HARD + ed);
-        const float mu = L.at(c, F_MU), Rp = L.at(c, F_R);
-        gram_step(v + NA, jn, j1, j2, ccf[k], ar, ia, hd, cfo[k], mu, Rp, Mi.Fd[0], improvement);
-      }
-    }
-  };
   // When no lane has a pre-block contact on the free body (always, for pair-ordered
   // scenes where the cube's world contacts come first), the block commutes with every
   // arm row before it: run it beside the friction rows so the two independent chains
@@ -1169,27 +1159,8 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
   const int ca = npost == 1 ? (c0 - npre > 0 ? npre : c1) : LDS_CON;
   auto xidx = [&](int j) { return j < c0 - npre ? npre + j : c1 + j - (c0 - npre); };  // j-th non-block contact
   auto sweeps = [&](auto first) {
-    for (int it = 0; it < m.iterations; it++) {
-      float improvement = 0.f;
-      if constexpr (decltype(first)::value) {
-        fric_rows(improvement);  // same basic block as the register block: they interleave
-        block_rows(improvement);
-        limit_rows(improvement);
-        for (int j = 0; j < npost; j++) lds_contact(j < c0 - npre ? npre + j : c1 + j - (c0 - npre), improvement);
-        scratch_rows(improvement);
-      } else {
-        fric_rows(improvement);
-        limit_rows(improvement);
-        for (int c = 0; c < npre; c++) lds_contact(c, improvement);
-        block_rows(improvement);
-        for (int j = 0; j < npost; j++) lds_contact(j < c0 - npre ? npre + j : c1 + j - (c0 - npre), improvement);
-        scratch_rows(improvement);
-      }
-      if (improvement * scale < m.tolerance) {
-        PROF_DO(nsweep = it + 1);
-        break;
-      }
-    }
+    vsweeps<CON>(first, m, L, cr, Mi, v, ff, fa, fR, fhD, fiD, cfo, ccf, cslot, nlim, nl, ncon, npre, npost, c0, c1,
+                 scale PROF_DECL(, nsweep));
   };
   PROF_DECL(bool pf_ypure = false, pf_yext = false, pf_yext2 = false, pf_ycoupled = false);  // (the y-form votes, for the profile record)
   // The free-body contact scene has two more solvers, the y-form block sweeps and (RS kernel) the
@@ -1883,175 +1854,10 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
     const bool ycoupled = yext && __any(npost >= 1 && ((int)L.at(cE, F_FLAGS) & TOUCH_FREE));
     const bool yext2 = yext && __any(npost == 2);
     PROF_DO(pf_ypure = ypure, pf_yext = yext, pf_yext2 = yext2, pf_ycoupled = ycoupled);
-    // ---- row-space PGS (RS kernel; see RS_MAXROW above).  Rows in mj_solPGS order: the NA dof
-    // frictionloss rows, the active limits, 4 pyramid edges per contact; NRB (compile time) bounds
-    // the rows of every env of the wave (rows past an env's own are zero rows: J = 0, so C's row and
-    // column are 0 and their steps are exact no-ops).  Lane r16 holds rows r16 (slot A) and 16 + r16
-    // (slot B, when NRB > 16).  v: the velocity after the warm start; on return, qacc.
-    auto rs_solve = [&](auto kat_c, auto kac_c) {
-      if constexpr (RS) {
-        using LY = RsLayout<NA, decltype(kat_c)::value, decltype(kac_c)::value>;
-        constexpr int NS = LY::NS, KAT = decltype(kat_c)::value, KAC = decltype(kac_c)::value;
-        const int r16 = L.lane & 15;
-        float* const Wl = L.rsw + L.col * RS_WENV;
-        // this lane's rows: slot A = CT edge r16, slot B = frictionloss row / AT edge / AC edge r16;
-        // kind 0 frictionloss, 1 pyramid edge, -1 none; c, ed: the edge's contact and edge index;
-        // qA / qB: the rows' step indices (their W rows in LDS)
-        const int cA = rs_nat + (r16 >> 2), qA = LY::CT0 + r16;
-        const int kindA = (r16 >> 2) < rs_nct ? 1 : -1;
-        int kindB = -1, cB = 0;
-        if (r16 < NA) {
-          kindB = 0;
-        } else if (r16 < LY::CT0) {
-          cB = (r16 - NA) >> 2, kindB = cB < rs_nat ? 1 : -1;
-        } else if (r16 < LY::CT0 + 4 * KAC) {
-          const int k = (r16 - LY::CT0) >> 2;
-          cB = rs_nat + rs_nct + k, kindB = k < rs_nac ? 1 : -1;
-        }
-        const int qB = r16 < LY::CT0 ? r16 : r16 + 16;
-        // row data: J (NV), aref, R, the warm-start force (the warm start above)
-        auto row_of = [&](int kind, int c, int ed, float (&J)[NV], float& ar, float& R, float& f) {
-#pragma unroll
-          for (int i = 0; i < NV; i++) J[i] = 0.f;
-          ar = 0.f, R = 1.f, f = 0.f;
-          if (kind == 0) {  // dof frictionloss row ed: J = e_ed
-#pragma unroll
-            for (int i = 0; i < NA; i++)
-              if (ed == i) {
-                J[i] = 1.f, ar = fa[i], R = fR[i];
-                // warm-start force (the Gram-form warm start's frictionloss branch)
-                const float fl = m.dof_frictionloss[i], jar = S.warm[i] - fa[i];
-                const float fs = (jar <= -fl * R) ? fl : (jar >= fl * R) ? -fl : -jar / R;
-                f = fl > 0.f ? fs : 0.f;
-              }
-          } else if (kind == 1) {  // pyramid edge J_n +- mu J_t of contact c
-            const float mu = L.at(c, F_MU), s = (ed & 1) ? -mu : mu;
-            const int t = 12 * (1 + (ed >> 1));
-#pragma unroll
-            for (int i = 0; i < NV; i++) J[i] = fmaf(s, L.at(c, t + i), L.at(c, i));
-            ar = L.at(c, F_AREF + ed), R = L.at(c, F_R);
-            float jar = -ar;  // warm-start force: the edge's J qacc_warmstart - aref, if negative
-#pragma unroll
-            for (int i = 0; i < NV; i++) jar = fmaf(J[i], S.warm[i], jar);
-            f = jar < 0.f ? -jar / R : 0.f;
-          }
-        };
-        float JA[NV], JB[NV], WA[NV], WB[NV], arA, arB, RA, RB, fA, fB;
-        row_of(kindA, cA, r16 & 3, JA, arA, RA, fA);
-        row_of(kindB, cB, kindB == 0 ? r16 : (r16 - NA) & 3, JB, arB, RB, fB);
-        Mi.mul(JA, WA, false, true);  // (CT rows touch the free body alone)
-        Mi.mul(JB, WB, true, KAC > 0);
-        // W rows to LDS, by step (the 4 copies of a quad write identical values)
-#pragma unroll
-        for (int i = 0; i < NV; i++) Wl[qA * RS_WROW + i] = WA[i];
-        if (qB < NS)
-#pragma unroll
-          for (int i = 0; i < NV; i++) Wl[qB * RS_WROW + i] = WB[i];
-        // AR_rr = J_r W_r + R_r
-        float ardA = RA, ardB = RB;
-#pragma unroll
-        for (int i = 0; i < NV; i++) ardA = fmaf(JA[i], WA[i], ardA), ardB = fmaf(JB[i], WB[i], ardB);
-        const float iA = 1.f / ardA, iB = 1.f / ardB;
-        const float hdA = 0.5f * ardA, hdB = 0.5f * ardB;
-        wave_sync();
-        // the bound registers, broadcast over the env's row: -f_q (edges) and the frictionloss
-        // rows' lo - f, hi - f
-        float NF_[NS], NH_[NA];
-        auto bounds = [&]() {
-          sfor<NS>([&](auto qc) {
-            constexpr int q = decltype(qc)::value;
-            const float fq = -rowbcast<LY::lane(q)>(LY::slot(q) == 0 ? fA : fB);
-            if constexpr (q < NA) {
-              const float fl = m.dof_frictionloss[q];
-              NF_[q] = fq - fl, NH_[q] = fq + fl;
-            } else {
-              NF_[q] = fq;
-            }
-          });
-        };
-        // v = qacc_smooth + sum_q W_q f_q (lane i < NV sums dof i, the row broadcasts it); f_q from the
-        // bound registers (NH_ = fl - f on the frictionloss rows, NF_ = -f on the others)
-        auto vel = [&]() {
-          float acc = 0.f;
-          const int di = r16 < NV ? r16 : 0;
-#pragma unroll
-          for (int q = 0; q < NS; q++)
-            acc = fmaf(Wl[q * RS_WROW + di], q < NA ? m.dof_frictionloss[q] - NH_[q] : -NF_[q], acc);
-          sfor<NV>([&](auto ic) {
-            constexpr int i = decltype(ic)::value;
-            v[i] = S.qacc_s[i] + rowbcast<i>(acc);
-          });
-        };
-        // the warm start in row space (the Gram-form block above is skipped on these waves): every
-        // row's warm force (row_of), v, and the dual cost against f = 0, summed over the env's rows
-        bounds();
-        vel();
-        float jvA = -arA, jvB = -arB, jqA = -arA, jqB = -arB;
-#pragma unroll
-        for (int i = 0; i < NV; i++) {
-          jvA = fmaf(JA[i], v[i], jvA), jvB = fmaf(JB[i], v[i], jvB);
-          jqA = fmaf(JA[i], S.qacc_s[i], jqA), jqB = fmaf(JB[i], S.qacc_s[i], jqB);
-        }
-        // dual cost: sum_r 0.5 f_r (J_r v - aref_r + R_r f_r) + 0.5 f_r (J_r qacc_smooth - aref_r)
-        const float wcost = rowsum16(0.5f * fA * (jvA + RA * fA) + 0.5f * fA * jqA +
-                                     (0.5f * fB * (jvB + RB * fB) + 0.5f * fB * jqB));
-        const bool rej = wcost > 0.f;  // worse than no warm start: f = 0, v = qacc_smooth
-        if (__any(rej)) {              // (wave-uniform: the broadcasts run on every row)
-          fA = rej ? 0.f : fA, fB = rej ? 0.f : fB;
-          bounds();
-#pragma unroll
-          for (int i = 0; i < NV; i++) v[i] = rej ? S.qacc_s[i] : v[i];
-          jvA = rej ? jqA : jvA, jvB = rej ? jqB : jvB;
-        }
-        f2 sA = f2{-fmaf(RA, fA, jvA) * iA, 0.f}, sB = f2{-fmaf(RB, fB, jvB) * iB, 0.f};
-        // the scaled matrix: C[r][q] = -J_r W_q / AR_rr, C[r][r] = -1, as (C, G) pairs: G is the row's
-        // own-step indicator, so the second accumulator takes the row's force step exactly (the stop
-        // test's Delta f_r; it was u_r - Delta s_r from an off-diagonal accumulator, whose fp32
-        // cancellation stopped an ill-conditioned env 22 sweeps early, 3.3e-3 m/s off -- r05); only
-        // the blocks a step updates
-        f2 CA[NS], CB[NS];
-        sfor<NS>([&](auto qc) {
-          constexpr int q = decltype(qc)::value;
-          constexpr bool UA = LY::upd_a(q), UB = LY::upd_b(q);
-          f2 a = f2{0.f, 0.f};
-#pragma unroll
-          for (int i = 0; i < NV; i++)
-            a = fma2(f2{UA ? JA[i] : 0.f, UB ? JB[i] : 0.f}, splat2(Wl[q * RS_WROW + i]), a);
-          const float ca = -a.x * iA, cb = -a.y * iB;
-          CA[q] = qA == q ? f2{-1.f, 1.f} : f2{ca, 0.f};
-          CB[q] = qB == q ? f2{-1.f, 1.f} : f2{cb, 0.f};
-          // (the W rows of two steps in flight at a time: hoisting every step's 12 LDS loads to
-          // the top would hold hundreds of values)
-          if constexpr (q & 1) __builtin_amdgcn_sched_barrier(0);
-        });
-        float scale = m.pgs_scale, tol = m.tolerance;
-        int iters = m.iterations;
-        // (loaded once: the sweeps' asm statements keep LICM from hoisting the model loads, which would
-        // otherwise be re-issued and waited for in every sweep)
-        asm volatile("" : "+s"(iters), "+s"(scale), "+s"(tol));
-        bool done = false;
-        PHASE_T(rp0);  // (the RS solve's split: prof_rs_split)
-        PROF_DECL(int wsw = 0);
-        for (int it = 0; it < iters; it++) {
-          PROF_DO(wsw = it + 1);
-          if (!done) {
-            PROF_DO(nsweep = it + 1);
-            const float s0A = sA.x, s0B = sB.x;
-            sA.y = 0.f, sB.y = 0.f;
-            rs_sweep<NA, LY>(sA, sB, CA, CB, NF_, NH_);
-            // improvement = sum_r AR_rr / 2 Delta f_r (s0 + s1)_r, Delta f_r = the row's own step (y)
-            float P = hdA * sA.y * (s0A + sA.x);
-            P = fmaf(hdB * sB.y, s0B + sB.x, P);
-            done = rowsum16(P) * scale < tol;
-          }
-          if (__all(done)) break;
-        }
-        PHASE_T(rp1);
-        // qacc = qacc_smooth + sum_q W_q f_q (NH_ = fl - f on the frictionloss rows, NF_ = -f on the
-        // others): lane i < NV sums dof i, then the row broadcasts it
-        vel();
-        PROF_DO(prof_rs_split(e, rp0, rp1, wsw));
-      }
+    // (soarm_rs.h)
+    auto rs_run = [&](auto kat, auto kac) {
+      rs_solve<decltype(kat)::value, decltype(kac)::value>(S, L, Mi, fa, fR, v, rs_nat, rs_nct,
+                                                           rs_nac PROF_DECL(, e, nsweep));
     };
     // wave-uniform choice: separate copies of the loop, no branch inside the sweep
     if constexpr (RS) {
@@ -2061,13 +1867,13 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
         int kat = __any(rs_nat >= 1) ? 1 : 0, kac = __any(rs_nac >= 1) ? 1 : 0;
         PROF_DO(if (g_rs_force11) kat = kac = 1);  // (diagnostic: every RS wave in the (1, 1) layout)
         if (kac == 1 && kat == 1)
-          rs_solve(O{}, O{});
+          rs_run(O{}, O{});
         else if (kac == 1)
-          rs_solve(Z{}, O{});
+          rs_run(Z{}, O{});
         else if (kat == 1)
-          rs_solve(O{}, Z{});
+          rs_run(O{}, Z{});
         else
-          rs_solve(Z{}, Z{});
+          rs_run(Z{}, Z{});
       } else {
         sweeps(std::false_type{});
       }
@@ -2098,31 +1904,7 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
 #pragma unroll
         for (int ed = 0; ed < 4; ed++) L.at(c0 + k, F_FRC + ed) = cfo[k][ed];
   }
-  if constexpr (RS) {
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < NA * (NA + 1) / 2; i++) S.LH[i] = L.kp(k++);
-#pragma unroll
-    for (int i = 0; i < NA; i++) S.DHi[i] = L.kp(k++);
-#pragma unroll
-    for (int i = 0; i < 6 * NF; i++) S.kf[i / 6][i % 6] = L.kp(k++);
-#pragma unroll
-    for (int i = 0; i < 3; i++) S.ee[i] = L.kp(k++);
-  } else if (L.keep) {
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < NA * (NA + 1) / 2; i++) S.MA[i] = L.kp(k++);
-#pragma unroll
-    for (int f2 = 0; f2 < NF; f2++)
-#pragma unroll
-      for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = 0; j <= i; j++) S.MF[f2][i * (i + 1) / 2 + j] = (i == j) ? L.kp(k++) : 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; i++) S.fsmooth[i] = L.kp(k++);
-#pragma unroll
-    for (int i = 0; i < 3; i++) S.ee[i] = L.kp(k++);
-  }
+  restore_kept<RS>(S, L);
   PROF_DO(if (e < 65536)
     g_pgs_prof[8 * e + 1] = clock64(), g_pgs_prof[8 * e + 2] = nsweep,
     g_pgs_prof[8 * e + 3] = (pf_ypure ? 0 : pf_yext ? 1 : block_first ? 2 : 3) | (npost > 0 && npost_free ? 16 : 0) |
@@ -2131,62 +1913,7 @@ DEVI int solve_constraints(Sim<NA, NF>& S, const float* __restrict__ cbuf, const
                             ((long long)(pf_yext ? 4 + 2 * pf_yext2 + pf_ycoupled : 0) << 28) | ((long long)(RS && !rs_fast) << 40) | ((long long)rs_why << 41),
     g_pgs_prof[8 * e + 4] = nlim, g_pgs_prof[8 * e + 5] = ncon);
 
-  // ---- qacc and qfrc_constraint = J' f
-#pragma unroll
-  for (int i = 0; i < NV; i++) {
-    S.qacc[i] = v[i];
-    S.fcon[i] = 0.f;
-  }
-  if constexpr (CON && RS) return ncon;  // (the RS kernel's Euler step needs qacc alone: integrate_qacc)
-  if constexpr (CON) {
-    // qacc = qacc_smooth + M^-1 J' f, so J' f = M qacc - qfrc_smooth (M qacc_smooth = qfrc_smooth):
-    // the Euler step's right-hand side qfrc_smooth + qfrc_constraint is M qacc.  One 6x6 product
-    // (+ the free bodies' diagonal blocks) instead of J' f over every contact row; equal in exact
-    // arithmetic, fp32 rounding apart (the oracle keeps J' f).
-#pragma unroll
-    for (int i = 0; i < NA; i++) {
-      float sacc = -S.fsmooth[i];
-#pragma unroll
-      for (int k = 0; k < NA; k++) sacc = fmaf(S.MA[i >= k ? i * (i + 1) / 2 + k : k * (k + 1) / 2 + i], v[k], sacc);
-      S.fcon[i] = sacc;
-    }
-#pragma unroll
-    for (int f = 0; f < NF; f++)
-#pragma unroll
-      for (int i = 0; i < 6; i++) {
-        const int d = NA + 6 * f + i;
-        S.fcon[d] = fmaf(S.MF[f][i * (i + 1) / 2 + i], v[d], -S.fsmooth[d]);
-      }
-    return ncon;
-  }
-#pragma unroll
-  for (int i = 0; i < NA; i++) S.fcon[i] += ff[i];
-  for (int l = 0; l < nlim; l++) {
-    float oh[NA];
-    one_hot<NA>((int)L.lm(l, L_DOF), oh);
-    const float t = L.lm(l, L_SGN) * L.lm(l, L_FRC);
-#pragma unroll
-    for (int k = 0; k < NA; k++) S.fcon[k] = fmaf(oh[k], t, S.fcon[k]);
-  }
-  for (int c = 0; c < nl; c++) {
-    float jn[NV], jt1[NV], jt2[NV];
-#pragma unroll
-    for (int i = 0; i < NV; i++) jn[i] = L.at(c, i), jt1[i] = L.at(c, 12 + i), jt2[i] = L.at(c, 24 + i);
-    const float mu = L.at(c, F_MU);
-#pragma unroll
-    for (int ed = 0; ed < 4; ed++) {
-      float J[NV];
-      edge_J<NV>(jn, jt1, jt2, ed, mu, J);
-      const float fr = L.at(c, F_FRC + ed);
-#pragma unroll
-      for (int i = 0; i < NV; i++) S.fcon[i] += J[i] * fr;
-    }
-  }
-  for (int r = 4 * nl; r < 4 * ncon; r++) {
-    const float fr = cr.S(r, 3);
-#pragma unroll
-    for (int i = 0; i < NV; i++) S.fcon[i] += cr.J(r, i) * fr;
-  }
+  write_qacc_fcon<CON, RS>(S, L, cr, v, ff, nlim, nl, ncon);
   return ncon;
 }
 

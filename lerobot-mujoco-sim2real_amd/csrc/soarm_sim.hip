@@ -1244,7 +1244,7 @@ int sim_phase_profile(double* out, int reset) {
   HIPCHECK(hipDeviceSynchronize());
   HIPCHECK(hipMemcpyFromSymbol(w.data(), HIP_SYMBOL(g_wphase), w.size() * sizeof(w[0])));
   HIPCHECK(hipMemcpyFromSymbol(nw, HIP_SYMBOL(g_newton), sizeof(nw)));
-  // per-wave rows (soarm_pgs.h g_wphase): maxima where g_phase's layout keeps a max, sums elsewhere
+  // per-wave rows (soarm_prof.h g_wphase): maxima where g_phase's layout keeps a max, sums elsewhere
   const auto is_max = [](int k) {
     return k == 8 || k == 10 || k == 15 || (k >= 23 && k <= 26) || k == 59 || k == 60 || (k >= 65 && k <= 68) ||
            k == 83;

@@ -100,7 +100,7 @@ DEVI void qpos0_contacts(const DModel& m, float* cbuf, int n, int e, PairMask& p
 // RS (PGS, free-body scene): the row-space kernel -- 16 lanes per env, 4 envs per wave.  The
 // per-env code runs on each of the env's 4 quads (identical values; the contact rows and the next
 // geom poses are split over the 16 lanes) and the constraint solve holds one row per lane
-// (soarm_pgs.h, RS_MAXROW): at 4096 envs 1024 waves, one per SIMD.
+// (soarm_rs.h, RS_MAXROW): at 4096 envs 1024 waves, one per SIMD.
 template <int NA, int NF, bool AP, int SOL, bool RS = false>
 __global__ __launch_bounds__(64) void k_substep(const DModel* __restrict__ dm, int n, sim_state st,
                                                 const float* __restrict__ action,

@@ -296,7 +296,7 @@ def _bench_states(name, n, steps, seed=0, nthreads=8):
 def test_one_substep_bench_state_mixed_contacts(gpu_lib, rs, monkeypatch):
     """One substep from late bench states (t = 120 env-steps of the contact workload): the
     cube's 4 resting contacts plus, in some envs, arm-table contacts (the waves that take
-    the general contact paths).  rs = "1": the row-space kernel (the default; soarm_pgs.h
+    the general contact paths).  rs = "1": the row-space kernel (the default; soarm_rs.h
     RsLayout), "0": the quad kernel (SOARM_RS=0)."""
     monkeypatch.setenv("SOARM_RS", rs)
     cm, orc, st, _ = _bench_states("contact", 512, 120)

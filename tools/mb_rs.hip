@@ -1,4 +1,4 @@
-// Diagnostic microbenchmark: cycles per row step of row-space PGS sweep patterns (soarm_pgs.h
+// Diagnostic microbenchmark: cycles per row step of row-space PGS sweep patterns (soarm_rs.h
 // rs_sweep), one wave per SIMD (1024 waves of 64 lanes, as the RS kernel at 4096 envs).
 //   hipcc --offload-arch=gfx950 -O3 -o tools/_mb/mb_rs tools/mb_rs.hip
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// Diagnostic microbenchmark: cycles per sweep of the RS kernel's row-space PGS (soarm_pgs.h rs_sweep),
+// Diagnostic microbenchmark: cycles per sweep of the RS kernel's row-space PGS (soarm_rs.h rs_sweep),
 // the sweep alone and inside the solve's stopping-test loop; one wave per SIMD (1024 waves).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/_mb/mb_rs2 tools/mb_rs2.hip
 #include <hip/hip_runtime.h>

@@ -88,7 +88,7 @@ for t in range(T):
                                      "mean_pgs_cycles": v[69 + i] / max(v[61 + i], 1),
                                      "mean_retire_sweep": v[73 + i] / max(v[61 + i], 1)}
                                  for i, k in enumerate(["E", "E_coupled", "EF", "EF_coupled"])}
-        if v[77 + 11] > 0:  # RS kernel split (soarm_pgs.h rs_solve, Newton profiler slots)
+        if v[77 + 11] > 0:  # RS kernel split (soarm_rs.h rs_solve, Newton profiler slots)
             w = v[77 + 11]
             r["rs"] = {"setup_cycles_per_wave": v[77 + 8] / w, "sweep_cycles_per_wave": v[77 + 9] / w,
                        "final_cycles_per_wave": v[77 + 10] / w, "sweeps_per_wave": v[77 + 16] / w,
