@@ -66,6 +66,7 @@ struct DModel {
   // k_collide's dispatch order (blockIdx.y -> pair): the pairs whose narrowphase is a convex-convex
   // solver or box-box clipping first (the launch's longest waves), plane pairs last
   int pair_order[MAXP];
+  int pair_rec[MAXP];  // the inverse: pair -> its dispatch slot = its PairRec (below)
   int ncq;
   int nslot;            // total contact slots (sum of per-pair capacities)
   int free_diag;        // every free body has ipos = 0 and iquat = 1: its 6x6 M block is diagonal
@@ -168,6 +169,80 @@ inline void lut_dir(int cell, double d[3]) {
     case 1: d[0] = u, d[1] = sg, d[2] = v; break;
     default: d[0] = u, d[1] = v, d[2] = sg; break;
   }
+}
+
+// ---- the collide's per-pair record.  k_collide row y (blockIdx.y) handles pair pair_order[y];
+// everything midphase and narrowphase read about that pair and its two geoms sits in record y of
+// an array the kernel takes as an argument, so a wave reaches its constants with one dependent
+// scalar load after the kernarg (through the DModel it was kernarg -> DModel -> pair_order ->
+// pair_geom1/2 -> geom_bodyid / geom_rbound / geom_cbody before the first body-frame load).
+// Copies of the DModel's values (pair_rec_make), so every result is the same.  The by-pair
+// callers (the CPU backend, the contacts at qpos0) reach the same records through
+// DModel::pair_rec, one code path.
+struct GeomRec {  // 32 dwords
+  int type, hullnum;  // SIM_GEOM_*; hull vertices (mesh)
+  // mesh: the geom's climbing records, cube-map cell records and support-bound table (the
+  // DModel's tables offset by geom_hulladr / geom_lutadr / geom_sbadr), and the overflow ids
+  const uint4 *rec, *lutrec;
+  const float* sb;
+  const uint16_t* ovf;
+  float pos[3], mat[9], center[3], half[3], size[3];
+  int geom;
+};
+enum : int { PREC_PLANE = 1, PREC_BOXBOX = 2, PREC_CONVEX = 4, PREC_NATIVE = 8 };  // PairRec::flags
+// dwords 0..15 of a record: all the bounding-sphere test needs -- a rejected row reads nothing else
+struct PairHead {
+  int pair, flags;  // PREC_*: geom1 a plane / box-box / box-mesh or mesh-mesh (the rows with a separating-axis cache)
+  int body1, body2;
+  float rbound1, rbound2, margin;
+  float cbody1[3], cbody2[3];
+  int slot, cap, cq;  // DModel pair_slot / pair_cap / pair_cq
+};
+struct alignas(256) PairRec : PairHead {
+  // dwords 16..31
+  int cqword;  // the count word's index in the pair mask ((npair + 31) / 32)
+  int _pad[15];
+  GeomRec g[2];
+};
+static_assert(sizeof(GeomRec) == 128 && sizeof(PairHead) == 64 && sizeof(PairRec) == 512, "PairRec layout");
+
+// records of geom g / pair p from the model's arrays (m's hull pointers: the device's or the host's)
+inline GeomRec geom_rec_make(const DModel& m, int g) {
+  GeomRec G{};
+  G.geom = g, G.type = m.geom_type[g], G.hullnum = m.geom_hullnum[g];
+  if (G.type == SIM_GEOM_MESH && m.geom_lutadr[g] >= 0) {
+    G.rec = m.hull_rec + (size_t)HULL_LUTREC * m.geom_hulladr[g];
+    G.lutrec = m.hull_lutrec + (size_t)HULL_LUTREC * m.geom_lutadr[g];
+    G.sb = m.hull_sb + m.geom_sbadr[g];
+    G.ovf = m.hull_ovf;
+  }
+  for (int k = 0; k < 3; k++) {
+    G.pos[k] = m.geom_pos[g][k], G.center[k] = m.geom_center[g][k];
+    G.half[k] = m.geom_half[g][k], G.size[k] = m.geom_size[g][k];
+  }
+  for (int k = 0; k < 9; k++) G.mat[k] = m.geom_mat[g][k];
+  return G;
+}
+inline PairRec pair_rec_make(const DModel& m, int p) {
+  PairRec r{};
+  const int gs[2] = {m.pair_geom1[p], m.pair_geom2[p]};
+  r.pair = p;
+  r.body1 = m.geom_bodyid[gs[0]], r.body2 = m.geom_bodyid[gs[1]];
+  r.rbound1 = m.geom_rbound[gs[0]], r.rbound2 = m.geom_rbound[gs[1]];
+  r.margin = m.pair_margin[p];
+  for (int k = 0; k < 3; k++) r.cbody1[k] = m.geom_cbody[gs[0]][k], r.cbody2[k] = m.geom_cbody[gs[1]][k];
+  r.slot = m.pair_slot[p], r.cap = m.pair_cap[p], r.cq = m.pair_cq[p];
+  r.cqword = (m.npair + 31) >> 5;
+  for (int i = 0; i < 2; i++) r.g[i] = geom_rec_make(m, gs[i]);
+  const int t1 = r.g[0].type, t2 = r.g[1].type;
+  if (t1 == SIM_GEOM_PLANE)
+    r.flags |= PREC_PLANE;
+  else if (t1 == SIM_GEOM_BOX && t2 == SIM_GEOM_BOX)
+    r.flags |= PREC_BOXBOX;
+  else if (t2 == SIM_GEOM_MESH && (t1 == SIM_GEOM_BOX || t1 == SIM_GEOM_MESH))
+    r.flags |= PREC_CONVEX;
+  if (m.ccd == SIM_CCD_NATIVE) r.flags |= PREC_NATIVE;
+  return r;
 }
 
 }  // namespace soarm

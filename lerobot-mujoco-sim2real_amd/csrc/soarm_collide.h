@@ -19,8 +19,12 @@
 #pragma once
 #include "soarm_step.h"
 #ifdef SOARM_DIAG_SUPPORT
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
+#include <map>
+#include <mutex>
+#include <vector>
 #endif
 
 namespace soarm {
@@ -114,6 +118,63 @@ inline void diag_support(int g, int cell, uint4 r0, int steps) {
   g_diag_sup_host.c[g][3] += steps;
   g_diag_prev_host[0] = key, g_diag_prev_host[1] = ans;
 }
+// (the same build: per pair, the distinct climbing records -- cube-map cell records and vertex
+// records -- one narrowphase call loads, and how many of them the same (pair, env) also loaded in
+// its previous call that loaded any: what a replay of last substep's records could prefetch.
+// SOARM_DIAG_REPEAT_JSON names a file for the counts, else they go to stderr)
+struct DiagRepeatHost {
+  struct PairStat {
+    unsigned long long calls = 0, distinct = 0, repeated = 0, loads = 0;
+    std::vector<int> hist;  // calls by their number of distinct records
+  };
+  std::mutex mu;
+  std::map<std::pair<int, int>, std::vector<const void*>> prev;  // (pair, env) -> its last call's records
+  std::map<int, PairStat> stat;
+  void call(int pair, int env, std::vector<const void*>& cur) {
+    if (cur.empty()) return;
+    const size_t loads = cur.size();
+    std::sort(cur.begin(), cur.end());
+    cur.erase(std::unique(cur.begin(), cur.end()), cur.end());
+    std::lock_guard<std::mutex> lk(mu);
+    std::vector<const void*>& pv = prev[{pair, env}];
+    PairStat& st = stat[pair];
+    std::vector<const void*> both;
+    std::set_intersection(cur.begin(), cur.end(), pv.begin(), pv.end(), std::back_inserter(both));
+    st.calls++, st.loads += loads, st.distinct += cur.size(), st.repeated += both.size();
+    if (st.hist.size() <= cur.size()) st.hist.resize(cur.size() + 1, 0);
+    st.hist[cur.size()]++;
+    pv = cur;
+    cur.clear();
+  }
+  ~DiagRepeatHost() {
+    const char* path = getenv("SOARM_DIAG_REPEAT_JSON");
+    FILE* f = path ? fopen(path, "w") : stderr;
+    if (!f) return;
+    fprintf(f, "{\"pairs\": [");
+    bool first = true;
+    for (auto& kv : stat) {
+      const PairStat& st = kv.second;
+      auto pct = [&](double q) {
+        unsigned long long acc = 0;
+        for (size_t k = 0; k < st.hist.size(); k++)
+          if ((acc += st.hist[k]) >= q * st.calls) return (int)k;
+        return (int)st.hist.size() - 1;
+      };
+      fprintf(f, "%s\n {\"pair\": %d, \"calls\": %llu, \"record_loads\": %llu, \"distinct\": %llu, \"repeated\": %llu, "
+                 "\"repeat_share\": %.4f, \"distinct_p50\": %d, \"distinct_p90\": %d, \"distinct_max\": %d}",
+              first ? "" : ",", kv.first, st.calls, st.loads, st.distinct, st.repeated,
+              st.distinct ? (double)st.repeated / st.distinct : 0.0, pct(0.5), pct(0.9), (int)st.hist.size() - 1);
+      first = false;
+    }
+    fprintf(f, "\n]}\n");
+    if (path) fclose(f);
+  }
+};
+inline DiagRepeatHost g_diag_repeat_host;
+inline thread_local std::vector<const void*> g_diag_recs_host;
+#define SOARM_DIAG_REC(p) g_diag_recs_host.push_back((const void*)(p))
+#else
+#define SOARM_DIAG_REC(p) ((void)0)
 #endif
 #if defined(SOARM_DIAG_SUPPORT) && SOARM_DEVICE_PASS
 // (diagnostic build: per geom, support queries, queries whose cube-map cell / answer repeats the
@@ -130,8 +191,8 @@ DEVI void diag_support(int g, int cell, uint4 r0, int steps) {
   g_diag_prev[0][t] = key, g_diag_prev[1][t] = ans;
 }
 #endif
-HDI float3 hull_support(const DModel& m, int g, const float l[3]) {
-  const gptr<uint4> rec = (gptr<uint4>)m.hull_rec + HULL_LUTREC * m.geom_hulladr[g];
+HDI float3 hull_support(const GeomRec& G, const float l[3]) {
+  const gptr<uint4> rec = (gptr<uint4>)G.rec;
 #if defined(SOARM_DIAG_SUPPORT)
   const int dcell = lut_cell(l[0], l[1], l[2]);
   int dsteps = 0;
@@ -139,11 +200,12 @@ HDI float3 hull_support(const DModel& m, int g, const float l[3]) {
   // the cell's copy of its start vertex's record, then per climbing step the record of the vertex
   // moved to: each carries its first 8 neighbours' coordinates, so a step is one round trip and
   // the last (no neighbour improves) none
-  const gptr<uint4> lr = (gptr<uint4>)m.hull_lutrec + HULL_LUTREC * (m.geom_lutadr[g] + lut_cell(l[0], l[1], l[2]));
+  const gptr<uint4> lr = (gptr<uint4>)G.lutrec + HULL_LUTREC * lut_cell(l[0], l[1], l[2]);
   uint4 r0 = ldg(lr, 0), nb[8];
+  SOARM_DIAG_REC(lr);
 #pragma unroll
   for (int k = 0; k < 8; k++) nb[k] = ldg(lr, 2 + k);
-  const int nvert = m.geom_hullnum[g];
+  const int nvert = G.hullnum;
   auto dotr = [&](const uint4& r) {
     return l[0] * fbits(r.x) + l[1] * fbits(r.y) + l[2] * fbits(r.z);
   };
@@ -162,7 +224,7 @@ HDI float3 hull_support(const DModel& m, int g, const float l[3]) {
       if (k == best) u = nb[k].w;
     const int deg = (int)(r0.w & 255u);
     if (deg > 8) {  // hub vertex (~2%): the rest of its neighbours, 8 per round trip
-      const gptr<uint16_t> ov = (gptr<uint16_t>)m.hull_ovf + (r0.w >> 8);
+      const gptr<uint16_t> ov = (gptr<uint16_t>)G.ovf + (r0.w >> 8);
       for (int a = 8; a < deg; a += 8) {
         uint32_t id[8];
         uint4 c[8];
@@ -181,6 +243,7 @@ HDI float3 hull_support(const DModel& m, int g, const float l[3]) {
     if (best < 0) break;
     const gptr<uint4> r = rec + HULL_LUTREC * u;
     r0 = ldg(r, 0), cd = nd;
+    SOARM_DIAG_REC(r);
 #pragma unroll
     for (int k = 0; k < 8; k++) nb[k] = ldg(r, 2 + k);
 #if defined(SOARM_DIAG_SUPPORT)
@@ -188,7 +251,7 @@ HDI float3 hull_support(const DModel& m, int g, const float l[3]) {
 #endif
   }
 #if defined(SOARM_DIAG_SUPPORT)
-  diag_support(g, dcell, r0, dsteps);
+  diag_support(G.geom, dcell, r0, dsteps);
 #endif
   return make_float3(fbits(r0.x), fbits(r0.y), fbits(r0.z));
 }
@@ -196,7 +259,7 @@ HDI float3 hull_support(const DModel& m, int g, const float l[3]) {
 // world support point of geom g (type uniform across the wave)
 // upper bound on a mesh hull's support value along a (not necessarily unit) local direction l
 // from the support-bound table (dmodel.h HULL_SB_K): 3 table loads, no hull data
-HDI float support_ub(const DModel& m, int g, const float l[3]) {
+HDI float support_ub(const GeomRec& G, const float l[3]) {
   const float a0 = fabsf(l[0]), a1 = fabsf(l[1]), a2 = fabsf(l[2]);
   int face;
   float u, v, mx;
@@ -211,23 +274,23 @@ HDI float support_ub(const DModel& m, int g, const float l[3]) {
   const float fu = fminf(fmaxf((u + mx) * s, 0.f), (float)HULL_SB_K), fv = fminf(fmaxf((v + mx) * s, 0.f), (float)HULL_SB_K);
   const int i = min((int)fu, HULL_SB_K - 1), j = min((int)fv, HULL_SB_K - 1);
   const float a = fu - i, b = fv - j;
-  const gptr<float> t = (gptr<float>)m.hull_sb + m.geom_sbadr[g] + face * HULL_SB_FACE + i * (HULL_SB_K + 1) + j;
+  const gptr<float> t = (gptr<float>)G.sb + face * HULL_SB_FACE + i * (HULL_SB_K + 1) + j;
   const float h00 = t[0], h10 = t[HULL_SB_K + 1], h01 = t[1], h11 = t[HULL_SB_K + 2];
   const float q = (a + b <= 1.f) ? (1.f - a - b) * h00 + a * h10 + b * h01
                                  : (a + b - 1.f) * h11 + (1.f - a) * h01 + (1.f - b) * h10;
   return mx * q;
 }
 
-HDI void support(const DModel& m, int g, const GeomPose& P, const float d[3], float out[3]) {
+HDI void support(const GeomRec& G, const GeomPose& P, const float d[3], float out[3]) {
   float l[3];
   mtv(l, P.R, d);
   float p[3] = {0, 0, 0};
-  const int t = m.geom_type[g];
+  const int t = G.type;
   if (t == SIM_GEOM_BOX) {
 #pragma unroll
-    for (int k = 0; k < 3; k++) p[k] = (l[k] >= 0.f ? 1.f : -1.f) * m.geom_size[g][k];
+    for (int k = 0; k < 3; k++) p[k] = (l[k] >= 0.f ? 1.f : -1.f) * G.size[k];
   } else if (t == SIM_GEOM_MESH) {
-    const float3 v = hull_support(m, g, l);
+    const float3 v = hull_support(G, l);
     p[0] = v.x, p[1] = v.y, p[2] = v.z;
   }
   float w[3];
@@ -235,8 +298,8 @@ HDI void support(const DModel& m, int g, const GeomPose& P, const float d[3], fl
   out[0] = P.p[0] + w[0], out[1] = P.p[1] + w[1], out[2] = P.p[2] + w[2];
 }
 
-HDI void geom_center(const DModel& m, int g, const GeomPose& P, float c[3]) {
-  const float lc[3] = {m.geom_center[g][0], m.geom_center[g][1], m.geom_center[g][2]};
+HDI void geom_center(const GeomRec& G, const GeomPose& P, float c[3]) {
+  const float lc[3] = {G.center[0], G.center[1], G.center[2]};
   float w[3];
   mv(w, P.R, lc);
   c[0] = P.p[0] + w[0], c[1] = P.p[1] + w[1], c[2] = P.p[2] + w[2];
@@ -254,13 +317,12 @@ struct MSup {
   float v[3], v1[3], v2[3];
 };
 struct MPair {
-  const DModel& m;
-  int g1, g2;
+  const GeomRec &G1, &G2;
   const GeomPose &P1, &P2;
   HDI void sup(const float d[3], MSup& s) const {
     const float nd[3] = {-d[0], -d[1], -d[2]};
-    support(m, g1, P1, d, s.v1);
-    support(m, g2, P2, nd, s.v2);
+    support(G1, P1, d, s.v1);
+    support(G2, P2, nd, s.v2);
     s.v[0] = s.v1[0] - s.v2[0], s.v[1] = s.v1[1] - s.v2[1], s.v[2] = s.v1[2] - s.v2[2];
   }
 };
@@ -313,8 +375,8 @@ HDI void expand(MSup p[4], const MSup& v4) {
 HDI void setsep(float sep[3], const float d[3]) { sep[0] = d[0], sep[1] = d[1], sep[2] = d[2]; }
 HDI int discover(const MPair& P, MSup p[4], float sep[3]) {
   float c1[3], c2[3], d[3], va[3], vb[3];
-  geom_center(P.m, P.g1, P.P1, c1);
-  geom_center(P.m, P.g2, P.P2, c2);
+  geom_center(P.G1, P.P1, c1);
+  geom_center(P.G2, P.P2, c2);
 #pragma unroll
   for (int k = 0; k < 3; k++) p[0].v1[k] = c1[k], p[0].v2[k] = c2[k], p[0].v[k] = c1[k] - c2[k];
   if (fz(p[0].v[0]) && fz(p[0].v[1]) && fz(p[0].v[2])) p[0].v[0] += 10.f * FEPS;
@@ -724,8 +786,8 @@ HDI bool gjk_complete(const MPair& P, GSup p[4], int n) {
 // thresholds are the oracle's (oracle_collision.c gjk_enclose), both in fp64.
 HDI bool gjk_enclose(const MPair& P, MSup q[4], float sep[3]) {
   float c1[3], c2[3];
-  geom_center(P.m, P.g1, P.P1, c1);
-  geom_center(P.m, P.g2, P.P2, c2);
+  geom_center(P.G1, P.P1, c1);
+  geom_center(P.G2, P.P2, c2);
   double x[3] = {(double)c1[0] - c2[0], (double)c1[1] - c2[1], (double)c1[2] - c2[2]};
   if (dotd(x, x) == 0.0) x[0] = 1e-9;
   GSup p[4];
@@ -950,12 +1012,12 @@ HDI void emit(PairOut& o, float dist, const float pos[3], const float n[3]) {
   o.n++;
 }
 
-HDI void plane_box(const DModel& m, int gp, int gb, const GeomPose& Pp, const GeomPose& Pb, PairOut& o) {
+HDI void plane_box(const GeomRec& Gb, const GeomPose& Pp, const GeomPose& Pb, PairOut& o) {
   const float n[3] = {Pp.R[2], Pp.R[5], Pp.R[8]};
   int cnt = 0;
   for (int i = 0; i < 8 && cnt < 4; i++) {
-    const float l[3] = {(i & 1 ? 1.f : -1.f) * m.geom_size[gb][0], (i & 2 ? 1.f : -1.f) * m.geom_size[gb][1],
-                        (i & 4 ? 1.f : -1.f) * m.geom_size[gb][2]};
+    const float l[3] = {(i & 1 ? 1.f : -1.f) * Gb.size[0], (i & 2 ? 1.f : -1.f) * Gb.size[1],
+                        (i & 4 ? 1.f : -1.f) * Gb.size[2]};
     float w[3], rel[3];
     mv(w, Pb.R, l);
     const float p[3] = {Pb.p[0] + w[0], Pb.p[1] + w[1], Pb.p[2] + w[2]};
@@ -969,11 +1031,11 @@ HDI void plane_box(const DModel& m, int gp, int gb, const GeomPose& Pp, const Ge
   }
 }
 
-HDI void plane_convex(const DModel& m, int gp, int g, const GeomPose& Pp, const GeomPose& Pg, PairOut& o) {
+HDI void plane_convex(const GeomRec& G, const GeomPose& Pp, const GeomPose& Pg, PairOut& o) {
   const float n[3] = {Pp.R[2], Pp.R[5], Pp.R[8]};
   const float nn[3] = {-n[0], -n[1], -n[2]};
   float p[3], rel[3];
-  support(m, g, Pg, nn, p);
+  support(G, Pg, nn, p);
   sub(rel, p, Pp.p);
   const float dist = dot3(rel, n);
   if (dist >= 0.f) return;
@@ -1038,8 +1100,8 @@ HDI int clip_poly8(const float in[8][3], int n, float out[8][3], const float o[3
   return k < 8 ? k : 8;
 }
 
-HDI void box_box(const DModel& m, int g1, int g2, const GeomPose& P1, const GeomPose& P2, PairOut& o) {
-  const float *h1 = m.geom_size[g1], *h2 = m.geom_size[g2];
+HDI void box_box(const GeomRec& G1, const GeomRec& G2, const GeomPose& P1, const GeomPose& P2, PairOut& o) {
+  const float *h1 = G1.size, *h2 = G2.size;
   float A[3][3], B[3][3], t[3];
 #pragma unroll
   for (int k = 0; k < 3; k++)
@@ -1264,8 +1326,7 @@ __device__ __forceinline__ void write_body_frames_lds(const Sim<NA, NF>& S, floa
 }
 
 // a body-frame point x in world coordinates from the env's frame of body b (b = 0: the world)
-HDI void body_point(const DModel& m, const float* __restrict__ gpose, int n, int e, int b, const float x[3],
-                    float w[3]) {
+HDI void body_point(const float* __restrict__ gpose, int n, int e, int b, const float x[3], float w[3]) {
   if (b == 0) {
     w[0] = x[0], w[1] = x[1], w[2] = x[2];
     return;
@@ -1277,9 +1338,8 @@ HDI void body_point(const DModel& m, const float* __restrict__ gpose, int n, int
 #pragma unroll
   for (int k = 0; k < 3; k++) w[k] += soa(gpose, b * BREC + k, n, e);
 }
-// geom g's world pose from its body's frame (the world body: the geom's own placement)
-HDI void load_pose(const DModel& m, const float* __restrict__ gpose, int n, int e, int g, GeomPose& o) {
-  const int b = m.geom_bodyid[g];
+// geom G's (of body b) world pose from its body's frame (the world body: the geom's own placement)
+HDI void load_pose(const GeomRec& G, int b, const float* __restrict__ gpose, int n, int e, GeomPose& o) {
   float bp[3] = {0.f, 0.f, 0.f}, bR[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
   if (b > 0) {
 #pragma unroll
@@ -1287,61 +1347,20 @@ HDI void load_pose(const DModel& m, const float* __restrict__ gpose, int n, int 
 #pragma unroll
     for (int k = 0; k < 9; k++) bR[k] = soa(gpose, b * BREC + 3 + k, n, e);
   }
-  const float gp[3] = {m.geom_pos[g][0], m.geom_pos[g][1], m.geom_pos[g][2]};
+  const float gp[3] = {G.pos[0], G.pos[1], G.pos[2]};
   float w[3];
   mv(w, bR, gp);
-  mm(o.R, bR, m.geom_mat[g]);
+  mm(o.R, bR, G.mat);
 #pragma unroll
   for (int c = 0; c < 3; c++) o.p[c] = bp[c] + w[c];
 }
 // the midphase bound of geom g at pose P: the world centre of its collision box and that box's
 // world-axis half-extents |R| h
-HDI void geom_bound(const DModel& m, int g, const GeomPose& P, float c[3], float h[3]) {
-  geom_center(m, g, P, c);
+HDI void geom_bound(const GeomRec& G, const GeomPose& P, float c[3], float h[3]) {
+  geom_center(G, P, c);
 #pragma unroll
   for (int k = 0; k < 3; k++)
-    h[k] = fabsf(P.R[3 * k]) * m.geom_half[g][0] + fabsf(P.R[3 * k + 1]) * m.geom_half[g][1] +
-           fabsf(P.R[3 * k + 2]) * m.geom_half[g][2];
-}
-
-// midphase of candidate pair p from the env's body frames: bounding spheres and, for a plane, the
-// other geom's bounding sphere above it (from the body frames alone), then world-aligned boxes of
-// the composed poses.  false: no contact is possible; P1 / P2 are set when it returns true.
-HDI bool midphase(const DModel& m, int p, const float* __restrict__ gpose, int n, int e, GeomPose& P1,
-                   GeomPose& P2) {
-  const int g1 = m.pair_geom1[p], g2 = m.pair_geom2[p];
-  if (m.geom_rbound[g1] > 0.f && m.geom_rbound[g2] > 0.f) {
-    // bounding spheres first, from the body frames and the centres' body-frame offsets (no geom
-    // pose composed for the ~80 of 86 pairs this rejects)
-    float c1[3], c2[3], r[3];
-    body_point(m, gpose, n, e, m.geom_bodyid[g1], m.geom_cbody[g1], c1);
-    body_point(m, gpose, n, e, m.geom_bodyid[g2], m.geom_cbody[g2], c2);
-    sub(r, c1, c2);
-    const float rr = m.geom_rbound[g1] + m.geom_rbound[g2] + m.pair_margin[p];
-    if (dot3(r, r) > rr * rr) return false;
-  }
-  if (m.geom_type[g1] == SIM_GEOM_PLANE && m.geom_rbound[g2] > 0.f) {
-    // bounding sphere of geom2 entirely above the plane (beyond the margin): no contact
-    float c2[3];
-    body_point(m, gpose, n, e, m.geom_bodyid[g2], m.geom_cbody[g2], c2);
-    load_pose(m, gpose, n, e, g1, P1);
-    const float h = (c2[0] - P1.p[0]) * P1.R[2] + (c2[1] - P1.p[1]) * P1.R[5] + (c2[2] - P1.p[2]) * P1.R[8];
-    if (h > m.geom_rbound[g2] + m.pair_margin[p]) return false;
-  }
-  load_pose(m, gpose, n, e, g1, P1);
-  load_pose(m, gpose, n, e, g2, P2);
-  if (m.geom_rbound[g1] > 0.f && m.geom_rbound[g2] > 0.f) {  // world-aligned boxes
-    float c1[3], h1[3], c2[3], h2[3], r[3];
-    geom_bound(m, g1, P1, c1, h1);
-    geom_bound(m, g2, P2, c2, h2);
-    sub(r, c1, c2);
-    const float mg = m.pair_margin[p];
-    bool sep = false;
-#pragma unroll
-    for (int k = 0; k < 3; k++) sep |= fabsf(r[k]) > h1[k] + h2[k] + mg;
-    if (sep) return false;
-  }
-  return true;
+    h[k] = fabsf(P.R[3 * k]) * G.half[0] + fabsf(P.R[3 * k + 1]) * G.half[1] + fabsf(P.R[3 * k + 2]) * G.half[2];
 }
 
 // Separating-axis cache of one env's candidate pairs, [pair*3 + k][env]: the axis of the last
@@ -1363,48 +1382,97 @@ struct SepCache {
     for (int k = 0; k < 3; k++) soa(a, 3 * p + k, n, e) = d[k];
   }
 };
+// midphase of candidate pair p from the env's body frames: bounding spheres and, for a plane, the
+// other geom's bounding sphere above it (from the body frames alone), then world-aligned boxes of
+// the composed poses.  false: no contact is possible; P1 / P2 are set when it returns true.
+// The record's head is read whole before the first test (on the device one wide scalar load, pinned
+// in registers: left to the compiler, each field is loaded in the branch that first needs it, one
+// dependent scalar round trip after another).
+HDI bool midphase(const PairRec& rec, const float* __restrict__ gpose, int n, int e, GeomPose& P1, GeomPose& P2) {
+  struct Rec : PairHead {
+    const GeomRec* g;
+  } pr{PairHead(rec), rec.g};
+#if SOARM_DEVICE_PASS
+  asm volatile(""
+               : "+s"(pr.pair), "+s"(pr.flags), "+s"(pr.body1), "+s"(pr.body2), "+s"(pr.rbound1), "+s"(pr.rbound2),
+                 "+s"(pr.margin), "+s"(pr.cbody1[0]), "+s"(pr.cbody1[1]), "+s"(pr.cbody1[2]), "+s"(pr.cbody2[0]),
+                 "+s"(pr.cbody2[1]), "+s"(pr.cbody2[2]), "+s"(pr.slot), "+s"(pr.cap), "+s"(pr.cq));
+#endif
+  if (pr.rbound1 > 0.f && pr.rbound2 > 0.f) {
+    // bounding spheres first, from the body frames and the centres' body-frame offsets (no geom
+    // pose composed for the ~80 of 86 pairs this rejects; the record's first 16 dwords)
+    float c1[3], c2[3], r[3];
+    body_point(gpose, n, e, pr.body1, pr.cbody1, c1);
+    body_point(gpose, n, e, pr.body2, pr.cbody2, c2);
+    sub(r, c1, c2);
+    const float rr = pr.rbound1 + pr.rbound2 + pr.margin;
+    if (dot3(r, r) > rr * rr) return false;
+  }
+  if ((pr.flags & PREC_PLANE) && pr.rbound2 > 0.f) {
+    // bounding sphere of geom2 entirely above the plane (beyond the margin): no contact
+    float c2[3];
+    body_point(gpose, n, e, pr.body2, pr.cbody2, c2);
+    load_pose(pr.g[0], pr.body1, gpose, n, e, P1);
+    const float h = (c2[0] - P1.p[0]) * P1.R[2] + (c2[1] - P1.p[1]) * P1.R[5] + (c2[2] - P1.p[2]) * P1.R[8];
+    if (h > pr.rbound2 + pr.margin) return false;
+  }
+  load_pose(pr.g[0], pr.body1, gpose, n, e, P1);
+  load_pose(pr.g[1], pr.body2, gpose, n, e, P2);
+  if (pr.rbound1 > 0.f && pr.rbound2 > 0.f) {  // world-aligned boxes
+    float c1[3], h1[3], c2[3], h2[3], r[3];
+    geom_bound(pr.g[0], P1, c1, h1);
+    geom_bound(pr.g[1], P2, c2, h2);
+    sub(r, c1, c2);
+    const float mg = pr.margin;
+    bool sep = false;
+#pragma unroll
+    for (int k = 0; k < 3; k++) sep |= fabsf(r[k]) > h1[k] + h2[k] + mg;
+    if (sep) return false;
+  }
+  return true;
+}
+
 // upper bound on geom g's support value along the local direction l (box: exact)
-HDI float support_ub_any(const DModel& m, int g, const float l[3]) {
-  if (m.geom_type[g] == SIM_GEOM_BOX)
-    return fabsf(l[0]) * m.geom_size[g][0] + fabsf(l[1]) * m.geom_size[g][1] + fabsf(l[2]) * m.geom_size[g][2];
-  return support_ub(m, g, l);
+HDI float support_ub_any(const GeomRec& G, const float l[3]) {
+  if (G.type == SIM_GEOM_BOX) return fabsf(l[0]) * G.size[0] + fabsf(l[1]) * G.size[1] + fabsf(l[2]) * G.size[2];
+  return support_ub(G, l);
 }
 // upper bound on max over (geom1 - geom2) of x.d: below zero proves the pair apart along d
-HDI float minkowski_ub(const DModel& m, int g1, int g2, const GeomPose& P1, const GeomPose& P2, const float d[3]) {
+HDI float minkowski_ub(const GeomRec& G1, const GeomRec& G2, const GeomPose& P1, const GeomPose& P2, const float d[3]) {
   float l1[3], l2[3];
   mtv(l1, P1.R, d);
   mtv(l2, P2.R, d);
   l2[0] = -l2[0], l2[1] = -l2[1], l2[2] = -l2[2];
   return (P1.p[0] - P2.p[0]) * d[0] + (P1.p[1] - P2.p[1]) * d[1] + (P1.p[2] - P2.p[2]) * d[2] +
-         support_ub_any(m, g1, l1) + support_ub_any(m, g2, l2);
+         support_ub_any(G1, l1) + support_ub_any(G2, l2);
 }
-// the cached axis of pair p still separates it
-HDI bool cached_apart(const DModel& m, int p, int g1, int g2, const GeomPose& P1, const GeomPose& P2,
-                       const SepCache& sc) {
+// the pair's cached axis still separates it
+HDI bool cached_apart(const PairRec& pr, const GeomPose& P1, const GeomPose& P2, const SepCache& sc) {
   float d[3];
-  sc.load(p, d);
+  sc.load(pr.pair, d);
   if (d[0] == 0.f && d[1] == 0.f && d[2] == 0.f) return false;
-  return minkowski_ub(m, g1, g2, P1, P2, d) < -(m.pair_margin[p] + SEP_MARGIN);
+  return minkowski_ub(pr.g[0], pr.g[1], P1, P2, d) < -(pr.margin + SEP_MARGIN);
 }
 
 // narrowphase of a pair that passed the midphase (geom types are uniform over a pair); CCD: the
-// convex-convex narrowphase fixed at compile time (SIM_CCD_*), or -1 to read it from the model
+// convex-convex narrowphase fixed at compile time (SIM_CCD_*), or -1 to read it from the record
 template <int CCD = -1>
-HDI void narrowphase(const DModel& m, int p, const GeomPose& P1, const GeomPose& P2, PairOut& o,
-                      const SepCache& sc, const EpaPool* pool = nullptr) {
+HDI void narrowphase(const PairRec& pr, const GeomPose& P1, const GeomPose& P2, PairOut& o, const SepCache& sc,
+                      const EpaPool* pool = nullptr) {
   o.n = 0;
   o.xc = 6;
-  const int g1 = m.pair_geom1[p], g2 = m.pair_geom2[p];
-  const int t1 = m.geom_type[g1], t2 = m.geom_type[g2];
+  const GeomRec &G1 = pr.g[0], &G2 = pr.g[1];
+  const int p = pr.pair;
+  const int t1 = G1.type, t2 = G2.type;
   if (t1 == SIM_GEOM_PLANE) {
     if (t2 == SIM_GEOM_BOX)
-      plane_box(m, g1, g2, P1, P2, o);
+      plane_box(G2, P1, P2, o);
     else if (t2 == SIM_GEOM_MESH)
-      plane_convex(m, g1, g2, P1, P2, o);
+      plane_convex(G2, P1, P2, o);
     return;
   }
   if (t1 == SIM_GEOM_BOX && t2 == SIM_GEOM_BOX) {
-    box_box(m, g1, g2, P1, P2, o);
+    box_box(G1, G2, P1, P2, o);
     return;
   }
   if (t1 == SIM_GEOM_BOX && t2 == SIM_GEOM_MESH) {
@@ -1412,17 +1480,17 @@ HDI void narrowphase(const DModel& m, int p, const GeomPose& P1, const GeomPose&
     // the hull's extreme point toward the box lies beyond that face, they are apart
     // (exact; MPR would find no contact).  One support query instead of an MPR run.
     float c2[3];
-    geom_center(m, g2, P2, c2);
+    geom_center(G2, P2, c2);
     const float r[3] = {c2[0] - P1.p[0], c2[1] - P1.p[1], c2[2] - P1.p[2]};
     float best = -3.0e38f, ax[3] = {0.f, 0.f, 1.f}, h = 0.f;
 #pragma unroll
     for (int k = 0; k < 3; k++) {
       const float a[3] = {P1.R[k], P1.R[3 + k], P1.R[6 + k]};
       const float dk = dot3(r, a);
-      const float gap = fabsf(dk) - m.geom_size[g1][k];
+      const float gap = fabsf(dk) - G1.size[k];
       if (gap > best) {
         const float sg = dk >= 0.f ? 1.f : -1.f;
-        best = gap, h = m.geom_size[g1][k];
+        best = gap, h = G1.size[k];
         ax[0] = sg * a[0], ax[1] = sg * a[1], ax[2] = sg * a[2];
       }
     }
@@ -1431,15 +1499,15 @@ HDI void narrowphase(const DModel& m, int p, const GeomPose& P1, const GeomPose&
       const float l[3] = {P2.R[0] * nd[0] + P2.R[3] * nd[1] + P2.R[6] * nd[2],
                           P2.R[1] * nd[0] + P2.R[4] * nd[1] + P2.R[7] * nd[2],
                           P2.R[2] * nd[0] + P2.R[5] * nd[1] + P2.R[8] * nd[2]};
-      const float lo = -support_ub(m, g2, l) + (P2.p[0] - P1.p[0]) * ax[0] + (P2.p[1] - P1.p[1]) * ax[1] +
+      const float lo = -support_ub(G2, l) + (P2.p[0] - P1.p[0]) * ax[0] + (P2.p[1] - P1.p[1]) * ax[1] +
                        (P2.p[2] - P1.p[2]) * ax[2] - h;  // <= the hull's distance beyond the face
-      if (lo > m.pair_margin[p] + SEP_MARGIN) return (void)(o.xc = 1);
+      if (lo > pr.margin + SEP_MARGIN) return (void)(o.xc = 1);
     }
-    if (cached_apart(m, p, g1, g2, P1, P2, sc)) return (void)(o.xc = 2);
+    if (cached_apart(pr, P1, P2, sc)) return (void)(o.xc = 2);
     float sp[3];
-    support(m, g2, P2, nd, sp);
+    support(G2, P2, nd, sp);
     const float dist = (sp[0] - P1.p[0]) * ax[0] + (sp[1] - P1.p[1]) * ax[1] + (sp[2] - P1.p[2]) * ax[2] - h;
-    if (dist > m.pair_margin[p]) return (void)(o.xc = 1);
+    if (dist > pr.margin) return (void)(o.xc = 1);
   }
   if (t1 == SIM_GEOM_MESH && t2 == SIM_GEOM_MESH) {
     // MPR's first test on support bounds: along d = c2 - c1 (MPR's first search direction) the
@@ -1448,8 +1516,8 @@ HDI void narrowphase(const DModel& m, int p, const GeomPose& P1, const GeomPose&
     // without the two hull support queries (persistently separated near pairs such as the
     // wrist/jaw meshes otherwise cost the collide kernel its longest waves)
     float c1[3], c2[3];
-    geom_center(m, g1, P1, c1);
-    geom_center(m, g2, P2, c2);
+    geom_center(G1, P1, c1);
+    geom_center(G2, P2, c2);
     float d[3] = {c2[0] - c1[0], c2[1] - c1[1], c2[2] - c1[2]};
     const float n2 = dot3(d, d);
     if (n2 > 1e-20f) {
@@ -1462,14 +1530,14 @@ HDI void narrowphase(const DModel& m, int p, const GeomPose& P1, const GeomPose&
                            -(P2.R[1] * d[0] + P2.R[4] * d[1] + P2.R[7] * d[2]),
                            -(P2.R[2] * d[0] + P2.R[5] * d[1] + P2.R[8] * d[2])};
       const float ub = (P1.p[0] - P2.p[0]) * d[0] + (P1.p[1] - P2.p[1]) * d[1] + (P1.p[2] - P2.p[2]) * d[2] +
-                       support_ub(m, g1, l1) + support_ub(m, g2, l2);
+                       support_ub(G1, l1) + support_ub(G2, l2);
       if (ub < -SEP_MARGIN) return (void)(o.xc = 1);
     }
-    if (cached_apart(m, p, g1, g2, P1, P2, sc)) return (void)(o.xc = 2);
+    if (cached_apart(pr, P1, P2, sc)) return (void)(o.xc = 2);
   }
-  MPair mp{m, g1, g2, P1, P2};
+  MPair mp{G1, G2, P1, P2};
   float depth, dir[3], pos[3], sep[3] = {0.f, 0.f, 0.f};
-  const bool native = CCD < 0 ? m.ccd == SIM_CCD_NATIVE : CCD == SIM_CCD_NATIVE;
+  const bool native = CCD < 0 ? (pr.flags & PREC_NATIVE) != 0 : CCD == SIM_CCD_NATIVE;
   if (native ? ccd_native(mp, depth, dir, pos, sep, pool) : mpr(mp, depth, dir, pos, sep)) {
     emit(o, -depth, pos, dir);
     o.xc = 5;
@@ -1479,18 +1547,18 @@ HDI void narrowphase(const DModel& m, int p, const GeomPose& P1, const GeomPose&
   sc.store(p, sep);
 }
 
-}  // namespace soarm
-
-namespace soarm {
-// midphase + narrowphase of candidate pair p of env e (geom records in gpose)
+// midphase + narrowphase of the candidate pair of record pr for env e (body frames in gpose)
 template <int CCD = -1>
-HDI void collide_pair(const DModel& m, int p, const float* __restrict__ gpose, int n, int e, PairOut& o,
+HDI void collide_pair(const PairRec& pr, const float* __restrict__ gpose, int n, int e, PairOut& o,
                        const SepCache& sc = SepCache{nullptr, 0, 0}, const EpaPool* pool = nullptr) {
   o.n = 0;
 #if defined(SOARM_DIAG_SUPPORT) && !SOARM_DEVICE_PASS
   g_diag_prev_host[0] = g_diag_prev_host[1] = ~0u;
 #endif
   GeomPose P1, P2;
-  if (midphase(m, p, gpose, n, e, P1, P2)) narrowphase<CCD>(m, p, P1, P2, o, sc, pool);
+  if (midphase(pr, gpose, n, e, P1, P2)) narrowphase<CCD>(pr, P1, P2, o, sc, pool);
+#if defined(SOARM_DIAG_SUPPORT) && !SOARM_DEVICE_PASS
+  g_diag_repeat_host.call(pr.pair, sc.e, g_diag_recs_host);  // (the CPU backend's sc.e is the env)
+#endif
 }
 }  // namespace soarm

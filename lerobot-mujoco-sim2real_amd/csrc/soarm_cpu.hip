@@ -34,6 +34,7 @@ struct CpuBatch {
   const sim_model* model = nullptr;
   int n = 0;
   DModel dm;                 // the model with host hull pointers
+  std::vector<PairRec> prec; // the collide's records (dmodel.h), reached by pair through dm.pair_rec
   // separating-axis cache [pair*3+k][env] (soarm_collide.h SepCache); mutable: each env's step
   // updates its own column through the const batch
   mutable std::vector<float> sepax;
@@ -90,7 +91,7 @@ int collide_env(const CpuBatch& B, Sim<NA, NF>& S, int e, CpuContact* con, int& 
   int nc = 0;
   for (int p = 0; p < m.npair; p++) {
     PairOut o{cbuf, 1, 0, 0, m.pair_cap[p], 0};  // the pair's slots, re-based to this scratch
-    collide_pair(m, p, gpose, 1, 0, o, SepCache{sep, B.n, e});
+    collide_pair(B.prec[m.pair_rec[p]], gpose, 1, 0, o, SepCache{sep, B.n, e});
     for (int k = 0; k < o.n; k++) {
       if (nc >= SIM_MAXCON) {
         status |= SIM_ST_CONOVERFLOW;
@@ -568,6 +569,8 @@ int cpu_batch_create(const sim_model* m, int n, CpuBatch** out) {
     c->dm.geom_lutadr[g] = g < m->desc.ngeom ? m->lutadr[g] : -1;
     c->dm.geom_sbadr[g] = g < m->desc.ngeom ? m->sbadr[g] : -1;
   }
+  c->prec.resize((size_t)std::max(c->dm.npair, 0));
+  for (int p = 0; p < c->dm.npair; p++) c->prec[c->dm.pair_rec[p]] = pair_rec_make(c->dm, p);
   if (!m->desc.disable_contact) c->sepax.assign((size_t)std::max(m->desc.npair, 1) * 3 * n, 0.f);
   *out = c;
   return SIM_OK;
@@ -596,7 +599,7 @@ int cpu_qpos0_contacts(sim_model* m) {
     float cb[PAIR_MAXCON * 7];
     for (int p = 0; p < d.npair; p++) {
       PairOut o{cb, 1, 0, 0, d.pair_cap[p], 0};
-      collide_pair(c->dm, p, gpose, 1, 0, o, SepCache{c->sepax.data(), 1, 0});
+      collide_pair(c->prec[d.pair_rec[p]], gpose, 1, 0, o, SepCache{c->sepax.data(), 1, 0});
       if (o.n == 0) continue;
       d.c0_w[p >> 5] |= 1u << (p & 31);
       if (d.pair_cq[p] >= 0) d.c0_w[nw] |= (uint32_t)(o.n - 1) << (2 * d.pair_cq[p]);
@@ -616,8 +619,9 @@ extern "C" int soarm_test_hull_support(const sim_model* m, int g, const float* d
     return soarm_set_error(SIM_E_ARG, "not a mesh geom");
   CpuBatch* c = nullptr;
   cpu_batch_create(m, 1, &c);
+  const GeomRec G = geom_rec_make(c->dm, g);
   for (int i = 0; i < nd; i++) {
-    const float3 v = hull_support(c->dm, g, dirs + 3 * i);
+    const float3 v = hull_support(G, dirs + 3 * i);
     out[3 * i] = v.x, out[3 * i + 1] = v.y, out[3 * i + 2] = v.z;
   }
   cpu_batch_free(c);

@@ -93,6 +93,7 @@ struct TraceRange {
 struct DevModel {
   int device = -1;
   DModel* d_model = nullptr;
+  PairRec* d_prec = nullptr;  // the collide's records in dispatch order (dmodel.h PairRec)
   float4* d_hv = nullptr;
   int32_t *d_hadr = nullptr, *d_hadj = nullptr;
   uint16_t* d_hlut = nullptr;
@@ -102,6 +103,7 @@ struct DevModel {
   void release() {
     (void)hipSetDevice(device);
     (void)hipFree(d_model);
+    (void)hipFree(d_prec);
     (void)hipFree(d_hv);
     (void)hipFree(d_hadr);
     (void)hipFree(d_hadj);
@@ -125,6 +127,7 @@ struct sim_batch {
   int n = 0, device = 0;
   CpuBatch* cpu = nullptr;     // device = -1: the CPU backend (soarm_cpu.hip) runs every call
   DModel* d_model = nullptr;   // shared per (model, device): DevModel
+  const PairRec* d_prec = nullptr;  // likewise: k_collide's per-row records
   float* d_scratch = nullptr;  // contact rows, [slot][env]
   size_t scratch_floats = 0;
   float* d_gpose = nullptr;    // body world frames [body*BREC+k][env] (soarm_collide.h load_pose)
@@ -176,11 +179,12 @@ struct sim_batch {
 #endif
 // CCD: one instantiation per narrowphase, so the MPR kernel carries none of EPA's private-memory
 // polytope (2.2 KB of scratch per lane)
-__device__ __forceinline__ int m_pair_order(const DModel* dm, int y) { return dm->pair_order[y]; }
+// prec: row blockIdx.y's pair record (DModel::pair_order: the heavy pairs dispatch first) -- the
+// kernel reads no other model data
 template <int CCD>
-__global__ __launch_bounds__(SOARM_COLLIDE_BLOCK, SOARM_COLLIDE_WAVES) void k_collide(const DModel* __restrict__ dm, int n,
+__global__ __launch_bounds__(SOARM_COLLIDE_BLOCK, SOARM_COLLIDE_WAVES) void k_collide(const PairRec* __restrict__ prec, int n,
                                                  const float* __restrict__ gpose,
-                                                 float* __restrict__ cbuf, int* __restrict__ ccount,
+                                                 float* __restrict__ cbuf,
                                                  uint32_t* __restrict__ pmask,
                                                  float* __restrict__ sepax,
                                                  unsigned long long* __restrict__ pcyc) {
@@ -196,32 +200,31 @@ __global__ __launch_bounds__(SOARM_COLLIDE_BLOCK, SOARM_COLLIDE_WAVES) void k_co
   }
   const EpaPool pool{s_epa, &s_epa_used, NSLOT};
   const int e = xcd_block() * blockDim.x + threadIdx.x;
-  const int p = m_pair_order(dm, blockIdx.y);  // (DModel::pair_order: the heavy pairs dispatch first)
   if (e >= n) return;
+  const PairRec& pr = prec[blockIdx.y];
+  const int p = pr.pair;
 #ifdef SOARM_DIAG_SKIPP
   if ((g_diag_skip[p >> 5] >> (p & 31)) & 1u) return;  // (diagnostic: the pairs SOARM_DIAG_SKIP names cost nothing)
 #endif
   const long long t0 = pcyc ? clock64() : 0;
-  const DModel& m = *dm;
-  PairOut o{cbuf, n, e, m.pair_slot[p], m.pair_cap[p], 0};
+  PairOut o{cbuf, n, e, pr.slot, pr.cap, 0};
 #ifdef SOARM_DIAG_SKIPP
   if (g_diag_stage == 1) {
     GeomPose P1, P2;
-    if (midphase(m, p, gpose, n, e, P1, P2)) soa(cbuf, 0, n, e) = P1.p[0] + P2.p[0];
+    if (midphase(pr, gpose, n, e, P1, P2)) soa(cbuf, 0, n, e) = P1.p[0] + P2.p[0];
     return;
   }
 #endif
-  collide_pair<CCD>(m, p, gpose, n, e, o, SepCache{sepax, n, e}, NSLOT > 0 ? &pool : nullptr);
+  collide_pair<CCD>(pr, gpose, n, e, o, SepCache{sepax, n, e}, NSLOT > 0 ? &pool : nullptr);
 #ifdef SOARM_DIAG_SKIPP
   if (g_diag_stage == 2) return;
 #endif
   // (no per-pair count is stored: the pair mask bit and, for multi-contact pairs, its 2-bit
   // count word carry it -- an empty pair costs no store)
-  (void)ccount;
   if (o.n > 0) {
     atomicOr(&pmask[(size_t)(p >> 5) * n + e], 1u << (p & 31));
-    const int cq = m.pair_cq[p];
-    if (cq >= 0) atomicOr(&pmask[(size_t)((m.npair + 31) >> 5) * n + e], (uint32_t)(o.n - 1) << (2 * cq));
+    const int cq = pr.cq;
+    if (cq >= 0) atomicOr(&pmask[(size_t)pr.cqword * n + e], (uint32_t)(o.n - 1) << (2 * cq));
   }
 #ifdef SOARM_COLLIDE_STATS
   // diagnostic build: per pair, how many envs each test decided (13-bit counters: codes 0-3 in
@@ -245,8 +248,8 @@ static void launch_collide(const sim_batch* b, hipStream_t q, unsigned long long
   if (const char* v = getenv("SOARM_DIAG_ROWS")) rows = std::min(rows, std::max(1, atoi(v)));
 #endif
   hipLaunchKernelGGL(kern, dim3((b->n + SOARM_COLLIDE_BLOCK - 1) / SOARM_COLLIDE_BLOCK, rows),
-                     dim3(SOARM_COLLIDE_BLOCK), 0, q, b->d_model, b->n,
-                     b->d_gpose, b->d_cbuf, b->d_ccount, b->d_pmask, b->d_sepax, pcyc);
+                     dim3(SOARM_COLLIDE_BLOCK), 0, q, b->d_prec, b->n,
+                     b->d_gpose, b->d_cbuf, b->d_pmask, b->d_sepax, pcyc);
 }
 
 // walk the pairs in order and append their contacts (deterministic indexing)
@@ -590,6 +593,7 @@ static int validate_and_build(const sim_model_desc& d, sim_model* M) {
     for (int c = 0; c < 3; c++)
       for (int p = d.npair - 1; p >= 0; p--)
         if (cls(p) == c) m.pair_order[k++] = p;
+    for (int y = 0; y < d.npair; y++) m.pair_rec[m.pair_order[y]] = y;
   }
   // free bodies: the kernels use a diagonal 6x6 mass block, which needs the inertia frame at
   // the body frame (ipos = 0, iquat = identity) — true for the build-defined cube
@@ -654,15 +658,20 @@ static int upload_into(const sim_model* m, DevModel* D) {
   }
   HIPCHECK(hipMalloc(&D->d_model, sizeof(DModel)));
   HIPCHECK(hipMemcpy(D->d_model, &dm, sizeof(DModel), hipMemcpyHostToDevice));
+  // the collide's records, from the same arrays (and this device's hull tables), in dispatch order
+  std::vector<PairRec> prec((size_t)std::max(dm.npair, 1));
+  for (int y = 0; y < dm.npair; y++) prec[y] = pair_rec_make(dm, dm.pair_order[y]);
+  HIPCHECK(hipMalloc(&D->d_prec, prec.size() * sizeof(PairRec)));
+  HIPCHECK(hipMemcpy(D->d_prec, prec.data(), prec.size() * sizeof(PairRec), hipMemcpyHostToDevice));
   return SIM_OK;
 }
 
 // the model's device copy on `device`: made by the first batch there, reused after
-static int upload_model(const sim_model* m, int device, DModel** out) {
+static int upload_model(const sim_model* m, int device, DModel** out, const PairRec** prec) {
   std::lock_guard<std::mutex> lk(m->mu);
   for (DevModel* d : m->dev)
     if (d->device == device) {
-      *out = d->d_model;
+      *out = d->d_model, *prec = d->d_prec;
       return SIM_OK;
     }
   DevModel* D = new DevModel();
@@ -674,7 +683,7 @@ static int upload_model(const sim_model* m, int device, DModel** out) {
     return rc;
   }
   m->dev.push_back(D);
-  *out = D->d_model;
+  *out = D->d_model, *prec = D->d_prec;
   return SIM_OK;
 }
 // the (struct_size, abi_version) header every by-pointer struct carries (soarm_sim.h)
@@ -961,7 +970,7 @@ int sim_batch_create(const sim_model* m, int n_envs, int device, sim_batch** out
   }
 #endif
   }
-  if (int rc = upload_model(m, device, &B->d_model)) {
+  if (int rc = upload_model(m, device, &B->d_model, &B->d_prec)) {
     delete B;
     return rc;
   }
