@@ -1,6 +1,6 @@
 // dmodel.h — device-side (float) model constants for the SO-ARM101 kernels.
 // Built on the host from sim_model_desc (include/soarm_sim.h) by
-// soarm_sim.hip:build_dmodel; lives in device global memory and is read with
+// soarm_model.hip:fill_dmodel; lives in device global memory and is read with
 // wave-uniform (scalar) loads.  Derived constants that MuJoCo recomputes every
 // step but that depend only on the model (frictionloss-row impedance, K/B of
 // each solref, rotation matrices of fixed quaternions) are folded here.
@@ -90,12 +90,8 @@ struct DModel {
   float act_gear[MAXU], act_gain[MAXU], act_bias[MAXU][3];
   float act_ctrlrange[MAXU][2], act_forcerange[MAXU][2];
 
-  // hull data (device pointers)
-  const float4* hull_vert;   // xyz; w = bits (adjacency start << 8 | degree) of the vertex
-  const int32_t* hull_adr;   // CSR offsets per global vertex (+1)
-  const int32_t* hull_adj;   // local neighbour ids
-  const uint16_t* hull_lut;  // per mesh geom: HULL_LUT_CELLS start vertices (cube-map of directions)
-  int geom_lutadr[MAXG];     // first LUT entry of each mesh geom (-1: not a mesh)
+  // hull data (device pointers), read through the collide's PairRec (geom_rec_make below)
+  int geom_lutadr[MAXG];  // first cube-map cell (HULL_LUT_CELLS per mesh geom) of each mesh geom (-1: not a mesh)
   // hill-climbing records, 160 B per vertex (HULL_LUTREC uint4): [0] x, y, z (float bits),
   // degree | overflow offset << 8; [1] the first 8 neighbour ids (local, uint16, padded with
   // the vertex itself); [2..9] those neighbours' x, y, z and local id.  Neighbours past 8 live

@@ -27,7 +27,7 @@
 
 #include "../../include/koopman_mpc.h"
 
-int soarm_set_error(int code, const std::string& msg);  // soarm_sim.hip (sim_last_error)
+int soarm_set_error(int code, const std::string& msg);  // soarm_model.hip (sim_last_error)
 
 namespace {
 

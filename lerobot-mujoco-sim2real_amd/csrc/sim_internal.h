@@ -1,23 +1,22 @@
-// sim_internal.h — what the library's two translation units share: the model object behind
-// the opaque `sim_model` handle, the error channel of sim_last_error(), and the CPU backend's
-// entry points (soarm_cpu.hip, `device = -1` in sim_batch_create; SURVEY.md §8(b) "Threading").
+// sim_internal.h — what the library's translation units share: the model object behind the
+// opaque `sim_model` handle (built by soarm_model.hip), the error channel of sim_last_error(),
+// the topology dispatch, and the CPU backend's entry points (soarm_cpu.hip, `device = -1` in
+// sim_batch_create; SURVEY.md §8(b) "Threading").
 #pragma once
 #include <cstdint>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/soarm_sim.h"
 #include "dmodel.h"
 
-struct DevModel;  // one device's copy of the model (soarm_sim.hip)
+struct DevModel;  // one device's copy of the model (soarm_sim.hip, which also defines ~sim_model)
 
 struct sim_model {
   sim_model_desc desc;
-  soarm::DModel dm;  // host copy; hull pointers filled per device upload (CPU backend: host vectors below)
-  std::vector<float4> hull_vert;
-  std::vector<int32_t> hull_adr, hull_adj;
-  std::vector<uint16_t> hull_lut;
+  soarm::DModel dm;  // host copy; its hull pointers stay null: bind_tables() makes a bound copy
   std::vector<uint4> hull_rec, hull_lutrec;  // climbing records (dmodel.h)
   std::vector<uint16_t> hull_ovf;
   std::vector<float> hull_sb;  // support-bound table (dmodel.h HULL_SB_K)
@@ -28,8 +27,53 @@ struct sim_model {
   ~sim_model();
 };
 
-// sets the calling thread's sim_last_error() text; returns code
+// sets the calling thread's sim_last_error() text; returns code (soarm_model.hip)
 int soarm_set_error(int code, const std::string& msg);
+
+// the (struct_size, abi_version) header every by-pointer struct carries (soarm_sim.h)
+template <class T>
+int check_struct(const T* p, const char* what) {
+  if (p->struct_size != (int32_t)sizeof(T) || p->abi_version != SIM_ABI_VERSION)
+    return soarm_set_error(SIM_E_ARG, std::string(what) +
+                                          ": struct_size / abi_version do not match this library (built for abi " +
+                                          std::to_string(SIM_ABI_VERSION) + ", sizeof " + std::to_string(sizeof(T)) + ")");
+  return SIM_OK;
+}
+
+// the model's DModel bound to one copy of its hull tables (a device's or the host vectors)
+inline soarm::DModel bind_tables(const sim_model& m, const uint4* rec, const uint4* lutrec, const uint16_t* ovf,
+                                 const float* sb) {
+  soarm::DModel dm = m.dm;
+  dm.hull_rec = rec, dm.hull_lutrec = lutrec, dm.hull_ovf = ovf, dm.hull_sb = sb;
+  for (int g = 0; g < SIM_MAXGEOM; g++) {
+    dm.geom_lutadr[g] = g < m.desc.ngeom ? m.lutadr[g] : -1;
+    dm.geom_sbadr[g] = g < m.desc.ngeom ? m.sbadr[g] : -1;
+  }
+  return dm;
+}
+// the collide's records of a bound DModel, in dispatch order (row y = pair pair_order[y])
+inline std::vector<soarm::PairRec> pair_records(const soarm::DModel& dm) {
+  std::vector<soarm::PairRec> prec((size_t)(dm.npair > 0 ? dm.npair : 0));
+  for (int y = 0; y < dm.npair; y++) prec[y] = soarm::pair_rec_make(dm, dm.pair_order[y]);
+  return prec;
+}
+
+// Supported topologies: arm chain of NA=6 hinges, NF in {0, 1} free bodies.
+template <class F>
+void dispatch_nf(int nf, F&& f) {
+  if (nf == 0)
+    f(std::integral_constant<int, 0>{});
+  else
+    f(std::integral_constant<int, 1>{});
+}
+// solver of the compiled model: PGS (the north star's) or MuJoCo's default Newton
+template <class F>
+void dispatch_sol(int sol, F&& f) {
+  if (sol == SIM_SOL_NEWTON)
+    f(std::integral_constant<int, SIM_SOL_NEWTON>{});
+  else
+    f(std::integral_constant<int, SIM_SOL_PGS>{});
+}
 
 // ---- CPU backend: the same per-env code as the kernels (soarm_step.h, soarm_collide.h,
 // soarm_env.h) compiled for the host, envs split over threads; the constraint solve is a

@@ -66,14 +66,6 @@ void parallel_envs(int n, F&& f) {
   for (auto& th : pool) th.join();
 }
 
-template <class F>
-void dispatch_nf(int nf, F&& f) {
-  if (nf == 0)
-    f(std::integral_constant<int, 0>{});
-  else
-    f(std::integral_constant<int, 1>{});
-}
-
 // one env's contacts at the current geom poses: collide every candidate pair (pair order,
 // each pair's contacts in slot order), at most SIM_MAXCON kept
 struct CpuContact {
@@ -556,21 +548,8 @@ int cpu_batch_create(const sim_model* m, int n, CpuBatch** out) {
   CpuBatch* c = new CpuBatch();
   c->model = m;
   c->n = n;
-  c->dm = m->dm;
-  c->dm.hull_vert = m->hull_vert.empty() ? nullptr : m->hull_vert.data();
-  c->dm.hull_adr = m->hull_adr.empty() ? nullptr : m->hull_adr.data();
-  c->dm.hull_adj = m->hull_adj.empty() ? nullptr : m->hull_adj.data();
-  c->dm.hull_lut = m->hull_lut.empty() ? nullptr : m->hull_lut.data();
-  c->dm.hull_rec = m->hull_rec.empty() ? nullptr : m->hull_rec.data();
-  c->dm.hull_lutrec = m->hull_lutrec.empty() ? nullptr : m->hull_lutrec.data();
-  c->dm.hull_ovf = m->hull_ovf.empty() ? nullptr : m->hull_ovf.data();
-  c->dm.hull_sb = m->hull_sb.empty() ? nullptr : m->hull_sb.data();
-  for (int g = 0; g < SIM_MAXGEOM; g++) {
-    c->dm.geom_lutadr[g] = g < m->desc.ngeom ? m->lutadr[g] : -1;
-    c->dm.geom_sbadr[g] = g < m->desc.ngeom ? m->sbadr[g] : -1;
-  }
-  c->prec.resize((size_t)std::max(c->dm.npair, 0));
-  for (int p = 0; p < c->dm.npair; p++) c->prec[c->dm.pair_rec[p]] = pair_rec_make(c->dm, p);
+  c->dm = bind_tables(*m, m->hull_rec.data(), m->hull_lutrec.data(), m->hull_ovf.data(), m->hull_sb.data());
+  c->prec = pair_records(c->dm);
   if (!m->desc.disable_contact) c->sepax.assign((size_t)std::max(m->desc.npair, 1) * 3 * n, 0.f);
   *out = c;
   return SIM_OK;

@@ -1,6 +1,6 @@
 """C-ABI boundary: the HIP library loads and exports exactly what include/soarm_sim.h declares.
 
-No compute calls here (no GPU in the CPU suite)."""
+No GPU calls here (the CPU suite has none; one test steps a CPU batch)."""
 import ctypes as C
 import os
 import re
@@ -124,6 +124,57 @@ def test_model_validation_rejects_unsupported():
     model = C.c_void_p()
     rc = lib.sim_model_create(C.byref(cm.desc), None, None, None, C.byref(model))
     assert rc == -2 and b"condim" in lib.sim_last_error()
+
+
+@pytest.mark.parametrize("missing", ["hull_vert", "hull_adr"])
+def test_model_create_rejects_missing_hull_arrays(missing):
+    """A valid desc with nhullvert > 0 and a null hull array is SIM_E_ARG (not a crash), and the
+    out handle stays null."""
+    import numpy as np
+    import soarm_pkg  # noqa: F401
+    from lerobot_mujoco_sim2real_amd import mjcf
+    cm = mjcf.compile_mjcf(mjcf.SCENE_XML)
+    assert cm.desc.nhullvert > 0
+    lib = abi.load_lib()
+    arrs = {"hull_vert": np.ascontiguousarray(cm.hull_vert, np.float32),
+            "hull_adr": np.ascontiguousarray(cm.hull_adr, np.int32),
+            "hull_adj": np.ascontiguousarray(cm.hull_adj, np.int32)}
+    args = [None if k == missing else a.ctypes.data_as(C.c_void_p) for k, a in arrs.items()]
+    model = C.c_void_p()
+    assert lib.sim_model_create(C.byref(cm.desc), *args, C.byref(model)) == -1
+    assert b"hull" in lib.sim_last_error() and not model
+
+
+def test_model_load_twice_same_cpu_step(tmp_path):
+    """The pick-scene model loaded, used by a CPU batch (2 envs, one env-step) and freed, twice in
+    one process: the second model's step output is bit-equal to the first's."""
+    import numpy as np
+    import soarm_pkg  # noqa: F401
+    from lerobot_mujoco_sim2real_amd import workloads as W
+    from lerobot_mujoco_sim2real_amd.sim import BatchSim, SimModel
+    cm = W.model("contact")
+    lib = abi.load_lib()
+    path = tmp_path / "pick.soarm"
+    cm.save(str(path))
+    ids = np.arange(2)
+    q0 = W.initial_qpos(cm, ids, 0)
+    act = W.chirp_action(W.chirp_tables(ids, 0), 0)
+
+    def run():
+        handle = SimModel.from_file(str(path), lib)
+        S = BatchSim(cm, 2, -1, model_handle=handle)
+        S.reset(init_qpos=q0[:, :5], extra_qpos=q0, seed=3)
+        S.step(act)
+        out = [x.numpy().copy() for x in (S.obs, S.qpos, S.qvel)]
+        S.close()
+        lib.sim_model_free(handle.ptr)
+        handle.ptr = None
+        return out
+
+    first, second = run(), run()
+    for a, b in zip(first, second):
+        assert np.isfinite(a).all() and np.array_equal(a, b)
+    assert np.abs(first[2]).max() > 0
 
 
 def test_philox_mirror_known_answer():
