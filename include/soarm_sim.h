@@ -337,6 +337,34 @@ int sim_ik_dls(sim_batch* b, const float* target, float* q, int32_t* ok, int32_t
 int sim_ik_dls_pose(sim_batch* b, const float* target, const float* target_quat, float* q, int32_t* ok,
                     int32_t* iters, const sim_ik_opts* opts, void* stream);
 
+/* replaces casadi_ik.Kinematics.ik (control/casadi_ik.py:27-167): per env and
+   frame the minimiser of
+     w_pos |p(q) - p*|^2 + w_rot |log3(R(q) R*')|^2 + w_smooth |q - q_last|^2
+   over the box of the joint ranges (jnt_range where jnt_limited), by a projected Gauss-Newton
+   method (soarm_ikbox.h).  The first `ndof` arm hinges move; the start is clamped
+   into the box and is q_last.  With nframe = F > 1 the frames are chained inside the call: frame
+   f starts from frame f-1's output, which is also its q_last, and a frame that does not converge
+   (ok = 0) outputs the last good solution (control/TrajectoryGenerator.py:180-205), for frame 0
+   the clamped start.  Every output lies inside the box, converged or not. */
+typedef struct sim_ik_box_opts {
+  int32_t struct_size;        /* sizeof(sim_ik_box_opts) */
+  int32_t abi_version;        /* SIM_ABI_VERSION */
+  double w_pos;               /* 10.0  casadi_ik.py:88 */
+  double w_rot;               /* 0.1   (unused when target_quat == NULL) */
+  double w_smooth;            /* 0.1   must be > 0 */
+  double tol;                 /* 1e-4  inf-norm of the projected gradient (ipopt tol, casadi_ik.py:96) */
+  int32_t max_steps;          /* 100 */
+  int32_t site;               /* site id */
+  int32_t ndof;               /* number of leading dofs moved (5) */
+  int32_t _pad;
+} sim_ik_box_opts;
+
+/* target [F][N][3]; target_quat [F][N][4] (w, x, y, z) or NULL (position only); q [nq][N] SoA in:
+   start, out: the last frame; q_traj [F][nq][N] or NULL; ok [F][N] (1 = converged); iters [F][N]
+   or NULL.  No allocation, copy or synchronisation: one launch on `stream`. */
+int sim_ik_box(sim_batch* b, int nframe, const float* target, const float* target_quat, float* q,
+               float* q_traj, int32_t* ok, int32_t* iters, const sim_ik_box_opts* opts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

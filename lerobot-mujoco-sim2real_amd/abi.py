@@ -105,6 +105,15 @@ class IkOpts(_Versioned):
     ]
 
 
+class IkBoxOpts(_Versioned):
+    """``sim_ik_box_opts``: the casadi_ik cost's weights and the projected-gradient tolerance."""
+    _fields_ = [
+        ("struct_size", i32), ("abi_version", i32),
+        ("w_pos", f64), ("w_rot", f64), ("w_smooth", f64), ("tol", f64),
+        ("max_steps", i32), ("site", i32), ("ndof", i32), ("_pad", i32),
+    ]
+
+
 class SimState(C.Structure):
     _fields_ = [
         ("qpos", C.c_void_p), ("qvel", C.c_void_p), ("qacc_warmstart", C.c_void_p),
@@ -135,6 +144,7 @@ EXPORTS = [
     "sim_batch_create", "sim_batch_free", "sim_batch_set_params", "sim_reset",
     "sim_step", "sim_substeps", "sim_bias", "sim_observe", "sim_contacts", "sim_collide_profile", "sim_phase_profile", "sim_ik_dls",
     "sim_profile_begin", "sim_profile_end", "sim_rand_uniform", "sim_ik_dls_pose",
+    "sim_ik_box",
     "sim_model_save", "sim_model_load",
     # include/koopman_mpc.h
     "sim_koopman_create", "sim_koopman_free", "sim_koopman_encode", "sim_koopman_feedforward",
@@ -180,6 +190,7 @@ def load_lib(path=None):
     lib.sim_profile_end.argtypes = [vp, vp, vp]
     lib.sim_ik_dls.argtypes = [vp, vp, vp, vp, vp, C.POINTER(IkOpts), vp]
     lib.sim_ik_dls_pose.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(IkOpts), vp]
+    lib.sim_ik_box.argtypes = [vp, ip, vp, vp, vp, vp, vp, vp, C.POINTER(IkBoxOpts), vp]
     lib.sim_rand_uniform.argtypes = [vp, C.c_uint64, C.c_int64, C.c_uint32, ip, C.c_float, C.c_float, vp, vp]
     lib.sim_koopman_create.argtypes = [C.POINTER(KoopmanDesc), vp, vp, ip, C.POINTER(vp)]
     lib.sim_koopman_free.argtypes = [vp]

@@ -9,6 +9,8 @@ call site passes — is position-only), warm-starting each point from the previo
 and repeating the last good solution on failure (``:180-205``).  Here the warm-started chain
 runs point by point through ``sim_ik_dls`` (one lane), and
 :meth:`solve_batch` solves many independent targets at once (one lane each).
+:meth:`generate_bounded` is the same path through the joint-limit-aware IK of
+``control/casadi_ik.py`` (``sim_ik_box``), the whole chain in one launch.
 """
 import numpy as np
 
@@ -44,18 +46,23 @@ class CartesianTrajectoryGenerator:
         t_param = 1.6 + 0.02 * np.linspace(0, self.time_horizon * 5, len(self.time_vector))
         return cartesian_targets(traj_name, t_param, self.idx, self.traj_scale)
 
-    def solve_batch(self, targets, q0=None, target_quat=None, **opts):
+    def solve_batch(self, targets, q0=None, target_quat=None, bounded=False, **opts):
         """Independent targets [N,3] (one lane each; target_quat [N,4] / [4] or None = position
-        only); returns q [N, nq], ok [N], iters [N]."""
+        only); returns q [N, nq], ok [N], iters [N].  bounded=True: the joint-limit-aware solve
+        (``BatchSim.ik_bounded``, the casadi_ik cost inside ``jnt_range``; opts are then its
+        w_pos / w_rot / w_smooth / tol / max_steps)."""
         import torch
 
-        o = dict(IK_DEFAULTS, **opts)
         targets = np.asarray(targets, dtype=np.float32)
         sim = self._sim(len(targets))
         q = None
         if q0 is not None:
             q = torch.as_tensor(np.asarray(q0, np.float32).T.copy(), device=sim.device)
-        q, ok, it = sim.ik(targets, q=q, ndof=self.num_joints, target_quat=target_quat, **o)
+        if bounded:
+            q, ok, it = sim.ik_bounded(targets, q=q, ndof=self.num_joints, target_quat=target_quat, **opts)
+        else:
+            q, ok, it = sim.ik(targets, q=q, ndof=self.num_joints, target_quat=target_quat,
+                               **dict(IK_DEFAULTS, **opts))
         return q.T.cpu().numpy(), ok.cpu().numpy().astype(bool), it.cpu().numpy()
 
     def generate(self, traj_name="Fig8", target_orientation=np.array([1.0, 0.0, 0.0, 0.0])):
@@ -81,3 +88,22 @@ class CartesianTrajectoryGenerator:
                 traj.append(traj[-1])
                 q = last
         return xyz, np.array(traj), self.time_vector
+
+    def generate_bounded(self, traj_name="Fig8", target_orientation=np.array([1.0, 0.0, 0.0, 0.0]), **opts):
+        """:meth:`generate` with the joint-limit-aware IK (``control/casadi_ik.py``; the alternative
+        the reference keeps commented out at ``control/TrajectoryGenerator.py:250-267``): every
+        point lies inside ``jnt_range``.  The whole path is one chained ``sim_ik_box`` call: point
+        i starts from point i-1's solution, which is also its smoothing anchor, and a point that
+        does not converge repeats the last good solution (``:180-205``).  The chain starts at
+        qpos0 clamped into the ranges.  Returns (xyz [N,3], q [N,num_joints], t [N])."""
+        import torch
+
+        xyz = self.cartesian_path(traj_name)
+        sim = self._sim(1)
+        tgt = np.ascontiguousarray(xyz, dtype=np.float32).reshape(len(xyz), 1, 3)
+        tq = None if target_orientation is None else np.asarray(target_orientation, np.float32).reshape(4)
+        q = torch.as_tensor(self.model.qpos0().astype(np.float32).reshape(-1, 1), device=sim.device).contiguous()
+        _, ok, _, traj = sim.ik_bounded(tgt, q=q, ndof=self.num_joints, target_quat=tq, **opts)
+        if not bool(ok[0, 0]):
+            raise RuntimeError("IK failed on the first trajectory point")
+        return xyz, traj[:, : self.num_joints, 0].cpu().numpy(), self.time_vector

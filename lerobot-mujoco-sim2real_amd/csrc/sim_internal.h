@@ -98,3 +98,5 @@ int cpu_rand_uniform(CpuBatch* c, uint64_t seed, int64_t env_offset, uint32_t co
                      float* out);
 int cpu_ik(CpuBatch* c, const float* target, const float* target_quat, float* q, int32_t* ok, int32_t* iters,
            const sim_ik_opts& o);
+int cpu_ik_box(CpuBatch* c, int nframe, const float* target, const float* target_quat, float* q, float* q_traj,
+               int32_t* ok, int32_t* iters, const sim_ik_box_opts& o);

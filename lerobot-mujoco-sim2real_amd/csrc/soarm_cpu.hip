@@ -6,7 +6,7 @@
 // soarm_step.h / soarm_collide.h / soarm_env.h): kinematics, CRBA + LDL', RNE + passive +
 // actuation, geom poses, the candidate-pair midphase and narrowphase (box-box, plane-*,
 // MPR or native GJK/EPA, with the separating-axis cache), implicit-damping Euler, resets,
-// observations, bias forces and DLS IK.  What differs is the constraint solve: the device
+// observations, bias forces, DLS IK and the box-bounded IK.  What differs is the constraint solve: the device
 // kernels' solvers are lane-cooperative (quad / 16-lane PGS sweeps, split Newton), so here
 // the rows are built densely in MuJoCo's order (dof frictionloss, joint limits lower/upper,
 // contacts x 4 pyramid edges; mj_makeConstraint) and solved by a scalar fp32 restatement of
@@ -27,6 +27,7 @@
 #include "sim_internal.h"
 #include "soarm_collide.h"
 #include "soarm_env.h"
+#include "soarm_ikbox.h"
 
 using namespace soarm;
 
@@ -693,5 +694,13 @@ int cpu_rand_uniform(CpuBatch* c, uint64_t seed, int64_t env_offset, uint32_t co
 int cpu_ik(CpuBatch* c, const float* target, const float* target_quat, float* q, int32_t* ok, int32_t* iters,
            const sim_ik_opts& o) {
   parallel_envs(c->n, [&](int e) { env_ik<6>(&c->dm, c->n, e, target, target_quat, q, ok, iters, o); });
+  return SIM_OK;
+}
+
+int cpu_ik_box(CpuBatch* c, int nframe, const float* target, const float* target_quat, float* q, float* q_traj,
+               int32_t* ok, int32_t* iters, const sim_ik_box_opts& o) {
+  parallel_envs(c->n, [&](int e) {
+    env_ik_box<6>(&c->dm, c->n, e, nframe, target, target_quat, q, q_traj, ok, iters, o);
+  });
   return SIM_OK;
 }

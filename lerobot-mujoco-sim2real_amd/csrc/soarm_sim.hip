@@ -7,6 +7,7 @@
 //   k_reset  : mj_resetData + init qpos/qvel + mj_forward + obs     (SOARM101_Env.py:77-106)
 //   k_observe: mj_kinematics + _get_state                           (SOARM101_Env.py:69-75)
 //   k_ik     : batched damped-least-squares site IK                 (control/TrajectoryGenerator.py:96-107)
+//   k_ik_box : batched box-bounded site IK, frames chained          (control/casadi_ik.py:27-167)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -34,6 +35,7 @@ __device__ uint32_t g_diag_prev[2][128 * 8192];
 #endif
 #include "soarm_collide.h"
 #include "soarm_env.h"
+#include "soarm_ikbox.h"
 #include "sim_internal.h"
 #include "soarm_pgs.h"
 
@@ -355,6 +357,17 @@ __global__ __launch_bounds__(64) void k_ik(const DModel* __restrict__ dm, int n,
                                            int32_t* __restrict__ iters, sim_ik_opts o) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e < n) env_ik<NA>(dm, n, e, target, tq, q, ok, iters, o);
+}
+
+// box-bounded site IK, the frames chained in the lane (soarm_ikbox.h env_ik_box)
+template <int NA>
+__global__ __launch_bounds__(64) void k_ik_box(const DModel* __restrict__ dm, int n, int nframe,
+                                               const float* __restrict__ target, const float* __restrict__ tq,
+                                               float* __restrict__ q, float* __restrict__ q_traj,
+                                               int32_t* __restrict__ ok, int32_t* __restrict__ iters,
+                                               sim_ik_box_opts o) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) env_ik_box<NA>(dm, n, e, nframe, target, tq, q, q_traj, ok, iters, o);
 }
 
 static inline dim3 grid_for(int n) { return dim3((n + 63) / 64); }
@@ -809,6 +822,26 @@ int sim_ik_dls_pose(sim_batch* b, const float* target, const float* target_quat,
 int sim_ik_dls(sim_batch* b, const float* target, float* q, int32_t* ok, int32_t* iters,
                const sim_ik_opts* opts, void* stream) {
   return sim_ik_dls_pose(b, target, nullptr, q, ok, iters, opts, stream);
+}
+
+int sim_ik_box(sim_batch* b, int nframe, const float* target, const float* target_quat, float* q,
+               float* q_traj, int32_t* ok, int32_t* iters, const sim_ik_box_opts* opts, void* stream) {
+  const TraceRange tr_("sim_ik_box");
+  if (opts)
+    if (int rc = check_struct(opts, "sim_ik_box_opts")) return rc;
+  if (!b || !target || !q || !ok || !opts) return fail(SIM_E_ARG, "null argument");
+  if (nframe < 1) return fail(SIM_E_ARG, "nframe must be >= 1");
+  // (negated comparisons: a NaN weight or tolerance is rejected too)
+  if (!(opts->w_smooth > 0.0) || !(opts->w_pos >= 0.0) || !(opts->w_rot >= 0.0) || !(opts->tol > 0.0))
+    return fail(SIM_E_ARG, "bad ik weights: need w_smooth > 0, w_pos >= 0, w_rot >= 0, tol > 0");
+  if (opts->site < 0 || opts->site >= b->model->desc.nsite) return fail(SIM_E_ARG, "ik site out of range");
+  if (opts->ndof < 1 || opts->ndof > 6 || opts->max_steps < 0) return fail(SIM_E_ARG, "bad ik options");
+  if (b->cpu) return cpu_ik_box(b->cpu, nframe, target, target_quat, q, q_traj, ok, iters, *opts);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((k_ik_box<6>), grid_for(b->n), dim3(64), 0, st, b->d_model, b->n, nframe, target, target_quat,
+                     q, q_traj, ok, iters, *opts);
+  HIPCHECK(hipGetLastError());
+  return SIM_OK;
 }
 
 }  // extern "C"

@@ -311,3 +311,47 @@ class BatchSim:
         abi.check(self.lib, self.lib.sim_ik_dls_pose(self._batch, _ptr(t), _ptr(tq), _ptr(q), _ptr(ok), _ptr(it),
                                                      C.byref(o), self._stream()))
         return q, ok, it
+
+    IK_BOX_DEFAULTS = dict(w_pos=10.0, w_rot=0.1, w_smooth=0.1, tol=1e-4, max_steps=100)
+
+    def ik_bounded(self, target, q=None, target_quat=None, ndof=5, site=None, **opts):
+        """Batched joint-limit-aware IK of a site (``sim_ik_box``; control/casadi_ik.py:27-167):
+        the minimiser of ``w_pos |p - p*|^2 + w_rot |log3(R R*')|^2 + w_smooth |q - q_last|^2``
+        inside ``jnt_range``, ``q_last`` = the start clamped into the ranges.
+
+        target [n, 3], or [F, n, 3]: F frames chained in one launch (frame f starts from frame
+        f-1's result; a frame that does not converge repeats the last good solution).
+        target_quat [4], [n, 4] or [F, n, 4] (w, x, y, z), or None (position only).
+        q [nq, n] start (SoA, modified in place: the last frame's result) or None (qpos0).
+        opts: w_pos, w_rot, w_smooth, tol, max_steps (IK_BOX_DEFAULTS).
+        Returns (q, ok, iters) with ok / iters [n], or for a 3-D target (q, ok, iters, q_traj)
+        with ok / iters [F, n] and q_traj [F, nq, n]."""
+        torch = self.torch
+        unknown = set(opts) - set(self.IK_BOX_DEFAULTS)
+        if unknown:
+            raise TypeError(f"ik_bounded: unknown options {sorted(unknown)}")
+        o = dict(self.IK_BOX_DEFAULTS, **opts)
+        t = torch.as_tensor(np.asarray(target, np.float32) if not isinstance(target, torch.Tensor) else target,
+                            dtype=torch.float32, device=self.device)
+        chained = t.dim() == 3
+        nf = t.shape[0] if chained else 1
+        t = t.reshape(nf, self.n, 3).contiguous()
+        tq = None
+        if target_quat is not None:
+            tq = torch.as_tensor(np.asarray(target_quat, np.float32) if not isinstance(
+                target_quat, torch.Tensor) else target_quat, dtype=torch.float32, device=self.device)
+            tq = tq.expand(nf, self.n, 4).contiguous()
+        if q is None:
+            q = torch.zeros((self.nq, self.n), dtype=torch.float32, device=self.device)
+            q[:] = self._dev(self.cm.qpos0()).reshape(-1, 1)
+        ok = torch.zeros((nf, self.n), dtype=torch.int32, device=self.device)
+        it = torch.zeros((nf, self.n), dtype=torch.int32, device=self.device)
+        traj = torch.zeros((nf, self.nq, self.n), dtype=torch.float32, device=self.device) if chained else None
+        ob = abi.IkBoxOpts(o["w_pos"], o["w_rot"], o["w_smooth"], o["tol"], int(o["max_steps"]),
+                           int(self.cm.desc.obs_site if site is None else site), int(ndof), 0)
+        self._keep_ik = (t, tq)
+        abi.check(self.lib, self.lib.sim_ik_box(self._batch, int(nf), _ptr(t), _ptr(tq), _ptr(q), _ptr(traj),
+                                                _ptr(ok), _ptr(it), C.byref(ob), self._stream()))
+        if chained:
+            return q, ok, it, traj
+        return q, ok[0], it[0]
