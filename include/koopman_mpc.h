@@ -22,6 +22,8 @@
  *   sim_koopman_mpc_step     z0 = Psi_o(x); u0; a = clip(u0); u_prev = u0 (one launch)
  *   sim_koopman_predict      the model's multi-step open-loop prediction of recorded trajectories
  *                            and its error (evaluate(), train.py:35-87; one launch for all steps)
+ *   sim_koopman_train_step   one training step of the DKUC model: loss, gradient and Adam in two
+ *                            launches (train(), train.py:89-266; k_linear_loss, models/losses.py:54-129)
  *
  * Arithmetic is float64 throughout, as in the reference (model.double(), Koopman_MPC.py:263).
  * Device buffers are caller-owned; calls are asynchronous on the given stream (void* =
@@ -120,6 +122,68 @@ int sim_koopman_bilinear_step(sim_koopman* k, int n, const double* z0, const dou
 int sim_koopman_set_model(sim_koopman* k, const double* A, const double* B, const double* Hhat);
 int sim_koopman_predict(sim_koopman* k, int n, int T, const float* rows, int ld, int x_off, int u_off,
                         int relift, int npos, double* pred, double* err, void* stream);
+
+/* Training (train(), train.py:89-266, with k_linear_loss, models/losses.py:54-129, loss_name "mse"):
+   one step of the DKUC model's fit is two launches -- the loss and its gradient, then the reduction
+   and Adam -- with no host synchronisation.
+
+   The trainer owns, on one device: the parameter vector (float64), Adam's m and v, the step count of
+   the bias correction, the MFMA-fragment copies the kernels read and a per-wave partial-gradient
+   workspace for max_batch windows.  The parameter vector, sim_koopman_trainer_nparam doubles, no
+   padding:  [W_0 | b_0 | ... | W_{nl-1} | b_{nl-1} | A (nz x nz row-major) | B (nz x u_dim row-major)]
+   -- the `weights` of sim_koopman_create, then the A and B of sim_koopman_set_model.  The decoder
+   lC = [I | 0] is frozen (models/KoopmanBase.py:38-43) and is no parameter.
+
+   Loss of n windows starting at row t0, P = pre_length, Psi(x) = [x, MLP(x)], beta_i = gamma^i,
+   cont = sum_i beta_i:   z^_0 = Psi(x_t0);  i < P:  z^_{i+1} = A z^_i + B u_{t0+i},
+     koopman = sum_i beta_i mean_{n nz}    (z^_{i+1} - Psi(x_{t0+i+1}))^2 / cont
+     pred    = sum_i beta_i mean_{n x_dim} (z^_{i+1}[:x_dim] - x_{t0+i+1})^2 / cont
+     dis / angle: pred over the columns < npos / >= npos, each with its own mean
+     recon   = 0 (lC Psi(x) = x exactly);   total = koopman + pred + recon.
+   The gradient is that of `total` with respect to the parameter vector (the two regularisers
+   k_linear_loss computes but leaves out of total_loss, losses.py:116-118, are not built).
+
+   opts: struct_size / abi_version as the other by-pointer structs; pre_length 1..64; npos
+   1..x_dim-1; gamma > 0; Adam's beta1, beta2, eps (torch.optim.Adam, no weight decay).
+   create: SIM_E_MODEL for a shape the kernels do not cover (nlayer > 5, LDS), SIM_E_NODEVICE
+   without a GPU; desc.horizon and desc.u_clip are validated as by sim_koopman_create and unused.
+   get_params / set_params: synchronous host copies; reset_optimizer != 0 zeroes m, v and the step count.
+
+   loss_grad / train_step: rows [T+1][N][ld] float32 as sim_koopman_predict reads them (x at x_off,
+   u at u_off; widened to float64); traj_idx [n] int32 on the device picks the window's trajectory
+   (repeats allowed; values are clamped to 0..N-1) or NULL for trajectories 0..n-1; t0 the window's
+   first row.  losses [6] device doubles (total, koopman, pred, recon, dis, angle) or NULL; grad
+   [nparam] device doubles or NULL.  loss_grad changes no trainer state.  train_step then applies
+       m <- beta1 m + (1 - beta1) g;  v <- beta2 v + (1 - beta2) g^2;
+       p <- p - lr / (1 - beta1^t) m / (sqrt(v) / sqrt(1 - beta2^t) + eps),   t = steps so far + 1
+   to the parameter vector and every fragment copy.  Partial gradients are summed in a fixed order
+   (no floating-point atomics): results are bitwise reproducible.  Neither call allocates, copies
+   between host and device or synchronises.
+   SIM_E_ARG before any launch: NULL tr or rows, n < 0, n > max_batch, N < 1, n > N with traj_idx
+   NULL, t0 < 0, t0 + pre_length > T, columns past ld.  n == 0 is a no-op. */
+typedef struct sim_koopman_train_opts {
+  int32_t struct_size; /* sizeof(sim_koopman_train_opts) */
+  int32_t abi_version; /* SIM_ABI_VERSION */
+  int32_t pre_length;  /* 5 */
+  int32_t npos;        /* 3: the dis / angle split of x */
+  double gamma;        /* 0.8 (args.py:68) */
+  double beta1;        /* 0.9 */
+  double beta2;        /* 0.999 */
+  double eps;          /* 1e-8 */
+} sim_koopman_train_opts;
+
+typedef struct sim_koopman_trainer sim_koopman_trainer;
+
+int sim_koopman_trainer_nparam(const sim_koopman_desc* desc);
+int sim_koopman_trainer_create(const sim_koopman_desc* desc, const double* params, int max_batch,
+                               const sim_koopman_train_opts* opts, int device, sim_koopman_trainer** out);
+void sim_koopman_trainer_free(sim_koopman_trainer* tr);
+int sim_koopman_trainer_get_params(sim_koopman_trainer* tr, double* host_params);
+int sim_koopman_trainer_set_params(sim_koopman_trainer* tr, const double* host_params, int reset_optimizer);
+int sim_koopman_loss_grad(sim_koopman_trainer* tr, int n, int N, int T, const float* rows, int ld, int x_off,
+                          int u_off, const int32_t* traj_idx, int t0, double* losses, double* grad, void* stream);
+int sim_koopman_train_step(sim_koopman_trainer* tr, int n, int N, int T, const float* rows, int ld, int x_off,
+                           int u_off, const int32_t* traj_idx, int t0, double lr, double* losses, void* stream);
 
 #ifdef __cplusplus
 }

@@ -131,6 +131,16 @@ class KoopmanDesc(C.Structure):
                 ("horizon", i32), ("_pad", i32), ("u_clip", f64)]
 
 
+class KoopmanTrainOpts(_Versioned):
+    """``sim_koopman_train_opts`` (include/koopman_mpc.h): the window length, the dis / angle split,
+    the step discount and Adam's constants (the reference's: args.py:68, torch.optim.Adam)."""
+    _fields_ = [
+        ("struct_size", i32), ("abi_version", i32),
+        ("pre_length", i32), ("npos", i32),
+        ("gamma", f64), ("beta1", f64), ("beta2", f64), ("eps", f64),
+    ]
+
+
 class SimParams(C.Structure):
     _fields_ = [("mass_scale", C.c_void_p), ("friction", C.c_void_p), ("damping_scale", C.c_void_p)]
 
@@ -150,6 +160,9 @@ EXPORTS = [
     "sim_koopman_create", "sim_koopman_free", "sim_koopman_encode", "sim_koopman_feedforward",
     "sim_koopman_mpc_step", "sim_koopman_set_bilinear", "sim_koopman_bilinear_step",
     "sim_koopman_set_model", "sim_koopman_predict",
+    "sim_koopman_trainer_nparam", "sim_koopman_trainer_create", "sim_koopman_trainer_free",
+    "sim_koopman_trainer_get_params", "sim_koopman_trainer_set_params",
+    "sim_koopman_loss_grad", "sim_koopman_train_step",
 ]
 PROF_KINDS = ["step_fused", "collide", "substep", "geom"]
 
@@ -202,6 +215,15 @@ def load_lib(path=None):
     lib.sim_koopman_bilinear_step.argtypes = [vp, ip, vp, vp, vp, vp, vp]
     lib.sim_koopman_set_model.argtypes = [vp, vp, vp, vp]
     lib.sim_koopman_predict.argtypes = [vp, ip, ip, vp, ip, ip, ip, ip, ip, vp, vp, vp]
+    lib.sim_koopman_trainer_nparam.argtypes = [C.POINTER(KoopmanDesc)]
+    lib.sim_koopman_trainer_create.argtypes = [C.POINTER(KoopmanDesc), vp, ip, C.POINTER(KoopmanTrainOpts), ip,
+                                               C.POINTER(vp)]
+    lib.sim_koopman_trainer_free.argtypes = [vp]
+    lib.sim_koopman_trainer_free.restype = None
+    lib.sim_koopman_trainer_get_params.argtypes = [vp, vp]
+    lib.sim_koopman_trainer_set_params.argtypes = [vp, vp, ip]
+    lib.sim_koopman_loss_grad.argtypes = [vp, ip, ip, ip, vp, ip, ip, ip, vp, ip, vp, vp, vp]
+    lib.sim_koopman_train_step.argtypes = [vp, ip, ip, ip, vp, ip, ip, ip, vp, ip, C.c_double, vp, vp]
     for name in EXPORTS:
         if not hasattr(lib, name):
             raise RuntimeError(f"{p} does not export {name}")

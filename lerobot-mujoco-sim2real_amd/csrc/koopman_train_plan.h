@@ -1,0 +1,244 @@
+// koopman_train_plan.h — the host-side plan of the Koopman trainer (koopman_train.hip): where every
+// parameter sits in the plain vector, where its copies sit in the MFMA-fragment blob the kernels
+// read, the workspace sizes, and the argument checks of the per-step calls.  Plain C++ (no HIP),
+// so tools/koopman_train_selftest.cpp runs it under the host sanitizers without a GPU.
+//
+// Parameter vector (sim_koopman_trainer_nparam doubles, no padding):
+//   [W_0 | b_0 | ... | W_{nl-1} | b_{nl-1} | A (nz x nz row-major) | B (nz x u_dim row-major)]
+// Fragment blob (doubles; every fragment is 64 lanes: lane l holds M[16 T + (l & 15)][4 s + (l >> 4)]
+// of output tile T and k-step s):
+//   encoder   W_l [ntile][ks][64] and the biases [nl][64], in KDev's layout (staged into LDS);
+//   wt[l]     W_l' for l >= 1: [4 (input tiles)][4 ntile[l]][64] (the backward's W' delta);
+//   ab        [A | B]: [1 + ntl][2 + 4 ntl + 2][64], tile 0 = the x rows, tiles 1.. = the features,
+//             k order [x (8) | features (16 ntl) | u (8)] (k_predict's);
+//   at        A': [1 + ntl][2 + 4 ntl][64] over the same tile and k orders.
+#ifndef KOOPMAN_TRAIN_PLAN_H
+#define KOOPMAN_TRAIN_PLAN_H
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/koopman_mpc.h"
+
+namespace ktrain {
+
+constexpr int MAXL = 5;         // encoder layers the wave's scratch plan covers (4 hidden x 64 rows)
+constexpr int MAXP = 64;        // pre_length
+constexpr int TILE_LD = 18;     // doubles per row of a wave's 16 x 16 transpose tile (see k_koopman_grad)
+constexpr int WAVES = 4;        // waves per workgroup
+constexpr size_t LDS_BYTES = 160 * 1024;
+
+struct Plan {
+  int xd, ud, nl, outw, nz, ntl, P, npos;
+  int width[SIM_KMAXLAYER + 1];
+  int ntile[SIM_KMAXLAYER], ks[SIM_KMAXLAYER], frag[SIM_KMAXLAYER];  // encoder (KDev's)
+  int bias, enc_total;                                             // doubles staged in LDS
+  int wt[SIM_KMAXLAYER], kst[SIM_KMAXLAYER];                       // W_l' fragments, their k-steps
+  int ab, abks, at, atks;
+  int blob_total;
+  int pw[SIM_KMAXLAYER], pb[SIM_KMAXLAYER], pA, pB, nparam;  // offsets into the parameter vector
+  // a wave's partial-gradient slot: every product's output tiles in the C/D layout, [tile][r][64]
+  // (lane l, register r = row (l >> 4) + 4 r, column l & 15 of the tile)
+  int sw[SIM_KMAXLAYER];  // dW_l: [ntile[l]][input tiles: 1 (l = 0) or 4]
+  int sb[SIM_KMAXLAYER];  // db_l: [64]
+  int sA;                 // [dA | dB]: [1 + ntl][1 + ntl + 1], the last tile column = dB
+  int slot_stride;   // doubles of a slot: the above + 8 (the loss sums)
+  int scr_stride;    // doubles of one wave's scratch: z^ and g [P][2][1 + ntl][4][64], then one
+                     // encode's hidden activations [MAXL - 1][4][4][64]
+  size_t lds_bytes;  // dynamic LDS of k_koopman_grad
+};
+
+// the shape checks of sim_koopman_create, then the trainer's own; fills pl.  SIM_OK or an error
+// code with its message in err
+inline int make_plan(const sim_koopman_desc& d, const sim_koopman_train_opts& o, Plan& pl, std::string& err) {
+  const int xd = d.x_dim, ud = d.u_dim, nl = d.nlayer;
+  if (xd < 1 || xd > SIM_KMAXX) return err = "x_dim must be in 1..8", SIM_E_MODEL;
+  if (ud < 1 || ud > SIM_KMAXU) return err = "u_dim must be in 1..8", SIM_E_MODEL;
+  if (nl < 2 || nl > SIM_KMAXLAYER) return err = "nlayer must be in 2..6", SIM_E_MODEL;
+  if (d.horizon < 1 || d.horizon > SIM_KMAXH) return err = "horizon must be in 1..32", SIM_E_MODEL;
+  if (d.width[0] != xd) return err = "width[0] must equal x_dim", SIM_E_MODEL;
+  for (int l = 1; l <= nl; l++)
+    if (d.width[l] < 1 || d.width[l] > SIM_KMAXW) return err = "encoder widths must be in 1..64", SIM_E_MODEL;
+  if (nl > MAXL)
+    return err = "trainer: nlayer must be <= 5 (the scratch plan keeps four hidden layers' activations)",
+           SIM_E_MODEL;
+  if (o.pre_length < 1 || o.pre_length > MAXP) return err = "trainer: pre_length must be in 1..64", SIM_E_ARG;
+  if (o.npos < 1 || o.npos >= xd) return err = "trainer: npos must be in 1..x_dim-1 (dis and angle are means)", SIM_E_ARG;
+  if (!(o.gamma > 0.0)) return err = "trainer: gamma must be positive", SIM_E_ARG;
+  if (!(o.beta1 >= 0.0 && o.beta1 < 1.0) || !(o.beta2 >= 0.0 && o.beta2 < 1.0) || !(o.eps >= 0.0))
+    return err = "trainer: beta1, beta2 must be in [0, 1) and eps >= 0", SIM_E_ARG;
+  pl = Plan{};
+  pl.xd = xd, pl.ud = ud, pl.nl = nl, pl.outw = d.width[nl], pl.nz = xd + d.width[nl];
+  pl.P = o.pre_length, pl.npos = o.npos;
+  for (int l = 0; l <= nl; l++) pl.width[l] = d.width[l];
+  int off = 0;
+  for (int l = 0; l < nl; l++) {
+    pl.ntile[l] = l == nl - 1 ? (d.width[l + 1] + 15) / 16 : 4;
+    pl.ks[l] = l == 0 ? 2 : 16;
+    pl.frag[l] = off;
+    off += pl.ntile[l] * pl.ks[l] * 64;
+  }
+  pl.ntl = pl.ntile[nl - 1];
+  pl.bias = off;
+  off += nl * SIM_KMAXW;
+  pl.enc_total = off;
+  for (int l = 1; l < nl; l++) {
+    pl.kst[l] = 4 * pl.ntile[l];
+    pl.wt[l] = off;
+    off += 4 * pl.kst[l] * 64;
+  }
+  pl.abks = 2 + 4 * pl.ntl + 2, pl.atks = 2 + 4 * pl.ntl;
+  pl.ab = off, off += (1 + pl.ntl) * pl.abks * 64;
+  pl.at = off, off += (1 + pl.ntl) * pl.atks * 64;
+  pl.blob_total = off;
+  int p = 0;
+  for (int l = 0; l < nl; l++) {
+    pl.pw[l] = p, p += d.width[l + 1] * d.width[l];
+    pl.pb[l] = p, p += d.width[l + 1];
+  }
+  pl.pA = p, p += pl.nz * pl.nz;
+  pl.pB = p, p += pl.nz * ud;
+  pl.nparam = p;
+  int so = 0;
+  for (int l = 0; l < nl; l++) {
+    pl.sw[l] = so, so += pl.ntile[l] * (l == 0 ? 1 : 4) * 256;
+    pl.sb[l] = so, so += 64;
+  }
+  pl.sA = so, so += (1 + pl.ntl) * (2 + pl.ntl) * 256;
+  pl.slot_stride = so + 8;
+  pl.scr_stride = pl.P * 2 * (1 + pl.ntl) * 4 * 64 + (MAXL - 1) * 4 * 4 * 64;
+  pl.lds_bytes = ((size_t)pl.enc_total + (size_t)WAVES * 16 * TILE_LD) * sizeof(double);
+  if (pl.lds_bytes > LDS_BYTES)
+    return err = "trainer: the encoder fragments and the transpose tiles (" + std::to_string(pl.lds_bytes) +
+                 " bytes) do not fit the 160 KiB of LDS",
+           SIM_E_MODEL;
+  return SIM_OK;
+}
+
+// lifted-state index of (tile, row in tile) / of padded k index kk; -1 = padding
+inline int z_of_row(const Plan& pl, int tile, int r) {
+  if (tile == 0) return r < pl.xd ? r : -1;
+  const int f = 16 * (tile - 1) + r;
+  return f < pl.outw ? pl.xd + f : -1;
+}
+inline int z_of_k(const Plan& pl, int kk) {
+  if (kk < 8) return kk < pl.xd ? kk : -1;
+  kk -= 8;
+  return (kk < 16 * pl.ntl && kk < pl.outw) ? pl.xd + kk : -1;
+}
+
+// map[c][p], c = 0, 1: the blob positions parameter p is copied to (-1 = none).  Every parameter has
+// one or two; false if a position is claimed twice or a parameter has none or more than two
+inline bool index_map(const Plan& pl, std::vector<int32_t>& map) {
+  map.assign((size_t)2 * pl.nparam, -1);
+  std::vector<uint8_t> used((size_t)pl.blob_total, 0);
+  bool ok = true;
+  auto put = [&](int p, int pos) {
+    if (p < 0 || p >= pl.nparam || pos < 0 || pos >= pl.blob_total || used[pos]) {
+      ok = false;
+      return;
+    }
+    used[pos] = 1;
+    if (map[p] < 0)
+      map[p] = pos;
+    else if (map[(size_t)pl.nparam + p] < 0)
+      map[(size_t)pl.nparam + p] = pos;
+    else
+      ok = false;
+  };
+  for (int l = 0; l < pl.nl; l++) {
+    const int in = pl.width[l], ou = pl.width[l + 1];
+    for (int T = 0; T < pl.ntile[l]; T++)
+      for (int s = 0; s < pl.ks[l]; s++)
+        for (int lane = 0; lane < 64; lane++) {
+          const int row = 16 * T + (lane & 15), col = 4 * s + (lane >> 4);
+          if (row < ou && col < in) put(pl.pw[l] + row * in + col, pl.frag[l] + (T * pl.ks[l] + s) * 64 + lane);
+        }
+    for (int r = 0; r < ou; r++) put(pl.pb[l] + r, pl.bias + l * SIM_KMAXW + r);
+    if (l >= 1)  // W_l': rows = the layer's inputs, k = its outputs
+      for (int T = 0; T < 4; T++)
+        for (int s = 0; s < pl.kst[l]; s++)
+          for (int lane = 0; lane < 64; lane++) {
+            const int row = 16 * T + (lane & 15), k = 4 * s + (lane >> 4);
+            if (row < in && k < ou) put(pl.pw[l] + k * in + row, pl.wt[l] + (T * pl.kst[l] + s) * 64 + lane);
+          }
+  }
+  for (int tile = 0; tile <= pl.ntl; tile++) {
+    for (int s = 0; s < pl.abks; s++)
+      for (int lane = 0; lane < 64; lane++) {
+        const int i = z_of_row(pl, tile, lane & 15), kk = 4 * s + (lane >> 4);
+        const int j = z_of_k(pl, kk), c = kk - (8 + 16 * pl.ntl);
+        const int pos = pl.ab + (tile * pl.abks + s) * 64 + lane;
+        if (i >= 0 && j >= 0) put(pl.pA + i * pl.nz + j, pos);
+        if (i >= 0 && c >= 0 && c < pl.ud) put(pl.pB + i * pl.ud + c, pos);
+      }
+    for (int s = 0; s < pl.atks; s++)
+      for (int lane = 0; lane < 64; lane++) {
+        const int j = z_of_row(pl, tile, lane & 15), i = z_of_k(pl, 4 * s + (lane >> 4));
+        if (i >= 0 && j >= 0) put(pl.pA + i * pl.nz + j, pl.at + (tile * pl.atks + s) * 64 + lane);
+      }
+  }
+  for (int p = 0; p < pl.nparam; p++)
+    if (map[p] < 0) ok = false;
+  return ok;
+}
+
+// position in a tile-ordered slot region (nti tile columns) of element (row, col)
+inline int slot_pos(int base, int nti, int row, int col) {
+  const int Tr = row >> 4, Tc = col >> 4, rr = row & 15, cc = col & 15;
+  return base + ((Tr * nti + Tc) * 4 + (rr >> 2)) * 64 + (rr & 3) * 16 + cc;
+}
+// padded row / column of lifted-state index z in the [x (16) | features] tile space
+inline int z_pad(const Plan& pl, int z) { return z < pl.xd ? z : 16 + (z - pl.xd); }
+
+// gidx[p]: where a wave's slot holds parameter p's gradient.  false if out of range or not one-to-one
+inline bool grad_index(const Plan& pl, std::vector<int32_t>& gidx) {
+  gidx.assign((size_t)pl.nparam, -1);
+  for (int l = 0; l < pl.nl; l++) {
+    const int in = pl.width[l], ou = pl.width[l + 1];
+    for (int r = 0; r < ou; r++) {
+      for (int c = 0; c < in; c++) gidx[pl.pw[l] + r * in + c] = slot_pos(pl.sw[l], l == 0 ? 1 : 4, r, c);
+      gidx[pl.pb[l] + r] = pl.sb[l] + r;
+    }
+  }
+  const int nti = 2 + pl.ntl;
+  for (int i = 0; i < pl.nz; i++) {
+    for (int j = 0; j < pl.nz; j++) gidx[pl.pA + i * pl.nz + j] = slot_pos(pl.sA, nti, z_pad(pl, i), z_pad(pl, j));
+    for (int c = 0; c < pl.ud; c++) gidx[pl.pB + i * pl.ud + c] = slot_pos(pl.sA, nti, z_pad(pl, i), 16 * (1 + pl.ntl) + c);
+  }
+  std::vector<uint8_t> used((size_t)pl.slot_stride, 0);
+  for (int p = 0; p < pl.nparam; p++) {
+    if (gidx[p] < 0 || gidx[p] >= pl.slot_stride - 8 || used[gidx[p]]) return false;
+    used[gidx[p]] = 1;
+  }
+  return true;
+}
+
+// the fragment blob of a parameter vector (zero padding)
+inline void pack_blob(const Plan& pl, const std::vector<int32_t>& map, const double* params, std::vector<double>& blob) {
+  blob.assign((size_t)pl.blob_total, 0.0);
+  for (int c = 0; c < 2; c++)
+    for (int p = 0; p < pl.nparam; p++) {
+      const int32_t pos = map[(size_t)c * pl.nparam + p];
+      if (pos >= 0) blob[pos] = params[p];
+    }
+}
+
+// the argument checks of sim_koopman_loss_grad / sim_koopman_train_step (before any launch)
+inline int check_step_args(const Plan& pl, int max_batch, int n, int N, int T, const void* rows, int ld, int x_off,
+                           int u_off, bool has_idx, int t0, std::string& err) {
+  if (!rows) return err = "null rows", SIM_E_ARG;
+  if (n < 0) return err = "n must be >= 0", SIM_E_ARG;
+  if (n > max_batch) return err = "n exceeds the trainer's max_batch", SIM_E_ARG;
+  if (N < 1 || T < 0) return err = "N must be >= 1 and T >= 0", SIM_E_ARG;
+  if (!has_idx && n > N) return err = "n exceeds N (traj_idx NULL reads trajectories 0..n-1)", SIM_E_ARG;
+  if (t0 < 0 || (long long)t0 + pl.P > T) return err = "the window t0 .. t0 + pre_length runs past row T", SIM_E_ARG;
+  if (ld < 1 || x_off < 0 || u_off < 0 || (long long)x_off + pl.xd > ld || (long long)u_off + pl.ud > ld)
+    return err = "the x / u columns run past the row length ld", SIM_E_ARG;
+  return SIM_OK;
+}
+
+}  // namespace ktrain
+#endif  // KOOPMAN_TRAIN_PLAN_H

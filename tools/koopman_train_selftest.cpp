@@ -1,0 +1,142 @@
+// koopman_train_selftest.cpp — the Koopman trainer's host-side code (csrc/koopman_train_plan.h: the
+// plan, the fragment index map, the slot gather index, blob packing, the per-step argument checks)
+// as a stand-alone program for the host sanitizers.  No GPU, no HIP:
+//
+//   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all
+//       tools/koopman_train_selftest.cpp -o /tmp/koopman_train_selftest && /tmp/koopman_train_selftest
+//
+// Prints "selftest ok" and exits 0; any mismatch aborts with a message.
+#include <cstdio>
+#include <cstdlib>
+#include <numeric>
+
+#include "../lerobot-mujoco-sim2real_amd/csrc/koopman_train_plan.h"
+
+#define REQUIRE(c)                                                  \
+  do {                                                              \
+    if (!(c)) {                                                     \
+      std::fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #c); \
+      std::exit(1);                                                 \
+    }                                                               \
+  } while (0)
+
+static sim_koopman_desc desc_of(std::vector<int> w, int ud) {
+  sim_koopman_desc d{};
+  d.x_dim = w[0], d.u_dim = ud, d.nlayer = (int)w.size() - 1, d.horizon = 10, d.u_clip = 0.5;
+  for (size_t i = 0; i < w.size(); i++) d.width[i] = w[i];
+  return d;
+}
+static sim_koopman_train_opts opts_of(int P, int npos) {
+  sim_koopman_train_opts o{};
+  o.struct_size = sizeof(o), o.abi_version = SIM_ABI_VERSION;
+  o.pre_length = P, o.npos = npos, o.gamma = 0.8, o.beta1 = 0.9, o.beta2 = 0.999, o.eps = 1e-8;
+  return o;
+}
+
+static void check_shape(std::vector<int> w, int ud, int P) {
+  using namespace ktrain;
+  const sim_koopman_desc d = desc_of(w, ud);
+  const sim_koopman_train_opts o = opts_of(P, 1);
+  Plan pl;
+  std::string err;
+  REQUIRE(make_plan(d, o, pl, err) == SIM_OK);
+  std::vector<int32_t> map, gidx;
+  REQUIRE(index_map(pl, map));
+  REQUIRE(grad_index(pl, gidx));
+  REQUIRE((int)map.size() == 2 * pl.nparam && (int)gidx.size() == pl.nparam);
+  std::vector<double> p(pl.nparam), blob;
+  std::iota(p.begin(), p.end(), 1.0);  // parameter i holds i + 1: a blob value names its parameter
+  pack_blob(pl, map, p.data(), blob);
+  REQUIRE((int)blob.size() == pl.blob_total);
+  // the encoder fragments as sim_koopman_create packs them, from the layout alone
+  const int nl = pl.nl;
+  for (int l = 0; l < nl; l++) {
+    const int in = w[l], ou = w[l + 1];
+    for (int T = 0; T < pl.ntile[l]; T++)
+      for (int s = 0; s < pl.ks[l]; s++)
+        for (int lane = 0; lane < 64; lane++) {
+          const int row = 16 * T + (lane & 15), col = 4 * s + (lane >> 4);
+          const double want = (row < ou && col < in) ? p[pl.pw[l] + row * in + col] : 0.0;
+          REQUIRE(blob[pl.frag[l] + (T * pl.ks[l] + s) * 64 + lane] == want);
+          if (l >= 1 && s < pl.kst[l] && T < 4) {  // W_l': row = an input, k = an output
+            const int r2 = 16 * T + (lane & 15), k2 = 4 * s + (lane >> 4);
+            const double wt = (r2 < in && k2 < ou) ? p[pl.pw[l] + k2 * in + r2] : 0.0;
+            REQUIRE(blob[pl.wt[l] + (T * pl.kst[l] + s) * 64 + lane] == wt);
+          }
+        }
+    for (int r = 0; r < SIM_KMAXW; r++) REQUIRE(blob[pl.bias + l * SIM_KMAXW + r] == (r < ou ? p[pl.pb[l] + r] : 0.0));
+  }
+  // [A | B] and A': tile 0 = the x rows, tile 1 + q = features 16 q ..; k order [x (8) | features | u (8)]
+  const int xd = w[0], outw = w[nl], nz = xd + outw, ntl = pl.ntl;
+  auto zrow = [&](int tile, int r) { return tile == 0 ? (r < xd ? r : -1) : (16 * (tile - 1) + r < outw ? xd + 16 * (tile - 1) + r : -1); };
+  auto zk = [&](int kk) { return kk < 8 ? (kk < xd ? kk : -1) : (kk - 8 < 16 * ntl && kk - 8 < outw ? xd + kk - 8 : -1); };
+  for (int tile = 0; tile <= ntl; tile++)
+    for (int lane = 0; lane < 64; lane++) {
+      for (int s = 0; s < pl.abks; s++) {
+        const int i = zrow(tile, lane & 15), kk = 4 * s + (lane >> 4), j = zk(kk), c = kk - 8 - 16 * ntl;
+        double want = 0.0;
+        if (i >= 0 && kk < 8 + 16 * ntl && j >= 0) want = p[pl.pA + i * nz + j];
+        if (i >= 0 && c >= 0 && c < ud) want = p[pl.pB + i * ud + c];
+        REQUIRE(blob[pl.ab + (tile * pl.abks + s) * 64 + lane] == want);
+      }
+      for (int s = 0; s < pl.atks; s++) {
+        const int j = zrow(tile, lane & 15), i = zk(4 * s + (lane >> 4));
+        REQUIRE(blob[pl.at + (tile * pl.atks + s) * 64 + lane] == ((i >= 0 && j >= 0) ? p[pl.pA + i * nz + j] : 0.0));
+      }
+    }
+  // sizes the kernels rely on
+  REQUIRE(pl.enc_total % 2 == 0 && pl.lds_bytes <= LDS_BYTES);
+  REQUIRE(pl.abks % 4 == 0 && pl.atks % 2 == 0);
+  REQUIRE(pl.scr_stride == P * 2 * (1 + ntl) * 256 + (MAXL - 1) * 1024);
+  for (int q = 0; q < pl.nparam; q++) REQUIRE(gidx[q] >= 0 && gidx[q] + 8 < pl.slot_stride + 1);
+  // the per-step argument checks
+  float rows = 0;
+  const int T = P + 3;
+  REQUIRE(check_step_args(pl, 32, 16, 20, T, &rows, 13, 5, 0, false, 0, err) == SIM_OK);
+  REQUIRE(check_step_args(pl, 32, 16, 20, T, &rows, 13, 5, 0, false, T - P, err) == SIM_OK);
+  REQUIRE(check_step_args(pl, 32, 0, 20, T, &rows, 13, 5, 0, false, 0, err) == SIM_OK);
+  REQUIRE(check_step_args(pl, 32, 16, 20, T, nullptr, 13, 5, 0, false, 0, err) == SIM_E_ARG);
+  REQUIRE(check_step_args(pl, 32, 33, 40, T, &rows, 13, 5, 0, false, 0, err) == SIM_E_ARG);
+  REQUIRE(check_step_args(pl, 32, -1, 20, T, &rows, 13, 5, 0, false, 0, err) == SIM_E_ARG);
+  REQUIRE(check_step_args(pl, 32, 16, 20, T, &rows, 13, 5, 0, false, -1, err) == SIM_E_ARG);
+  REQUIRE(check_step_args(pl, 32, 16, 20, T, &rows, 13, 5, 0, false, T - P + 1, err) == SIM_E_ARG);
+  REQUIRE(check_step_args(pl, 32, 16, 20, T, &rows, 13, 5, 0, false, 2147483647, err) == SIM_E_ARG);
+  REQUIRE(check_step_args(pl, 32, 16, 20, T, &rows, 13, 13 - xd + 1, 0, false, 0, err) == SIM_E_ARG);
+  REQUIRE(check_step_args(pl, 32, 16, 20, T, &rows, 13, 5, 13 - ud + 1, false, 0, err) == SIM_E_ARG);
+  REQUIRE(check_step_args(pl, 32, 16, 20, T, &rows, 2147483647, 2147483647 - 2, 0, false, 0, err) == SIM_E_ARG);
+  REQUIRE(check_step_args(pl, 32, 16, 8, T, &rows, 13, 5, 0, false, 0, err) == SIM_E_ARG);
+  REQUIRE(check_step_args(pl, 32, 16, 8, T, &rows, 13, 5, 0, true, 0, err) == SIM_OK);
+  REQUIRE(check_step_args(pl, 32, 16, 0, T, &rows, 13, 5, 0, true, 0, err) == SIM_E_ARG);
+}
+
+int main() {
+  using namespace ktrain;
+  check_shape({8, 64, 64, 64, 64, 24}, 5, 5);  // the reference's encoder
+  check_shape({8, 64, 64, 40}, 5, 1);          // three last-layer tiles
+  check_shape({8, 64, 64}, 5, 5);              // four
+  check_shape({3, 17, 5}, 1, 64);              // odd widths, one tile, the longest window
+  check_shape({8, 33, 64, 1, 16}, 8, 2);
+  // refusals
+  Plan pl;
+  std::string err;
+  sim_koopman_desc d = desc_of({8, 64, 64, 64, 64, 64, 24}, 5);
+  sim_koopman_train_opts o = opts_of(5, 3);
+  REQUIRE(make_plan(d, o, pl, err) == SIM_E_MODEL);  // nlayer 6
+  d = desc_of({8, 64, 65}, 5);
+  REQUIRE(make_plan(d, o, pl, err) == SIM_E_MODEL);
+  d = desc_of({8, 64, 24}, 5);
+  d.horizon = 0;
+  REQUIRE(make_plan(d, o, pl, err) == SIM_E_MODEL);
+  d.horizon = 10;
+  for (int bad = 0; bad < 5; bad++) {
+    o = opts_of(5, 3);
+    if (bad == 0) o.pre_length = 0;
+    if (bad == 1) o.pre_length = MAXP + 1;
+    if (bad == 2) o.npos = 8;
+    if (bad == 3) o.gamma = 0.0;
+    if (bad == 4) o.beta2 = 1.0;
+    REQUIRE(make_plan(d, o, pl, err) == SIM_E_ARG && !err.empty());
+  }
+  std::puts("selftest ok");
+  return 0;
+}
