@@ -160,7 +160,23 @@ int sim_koopman_predict(sim_koopman* k, int n, int T, const float* rows, int ld,
    (no floating-point atomics): results are bitwise reproducible.  Neither call allocates, copies
    between host and device or synchronises.
    SIM_E_ARG before any launch: NULL tr or rows, n < 0, n > max_batch, N < 1, n > N with traj_idx
-   NULL, t0 < 0, t0 + pre_length > T, columns past ld.  n == 0 is a no-op. */
+   NULL, t0 < 0, t0 + pre_length > T, columns past ld.  n == 0 is a no-op.
+
+   The bilinear DBKN model (models/KoopmanBase.py:62-78; the same train() and k_linear_loss):
+   sim_koopman_trainer_create_bilinear makes a trainer of the same handle type whose step is
+       z^_{i+1} = A z^_i + B u_{t0+i} + H vec(z^_i (x) u_{t0+i})      (u_z = 0)
+                                      + H vec(u_{t0+i} (x) z^_i)      (u_z = 1)
+   with everything else -- the losses, the encoder, Adam, the calls above, their refusals -- as for
+   DKUC.  Its parameter vector is DKUC's followed by one block, sim_koopman_trainer_nparam_bilinear =
+   sim_koopman_trainer_nparam + nz nz u_dim doubles:
+       [... | A | B | H (nz x nz u_dim row-major)],
+   H exactly as net.H.weight in the net's own u_z order: column j u_dim + c multiplies z_j u_c for
+   u_z = 0, column c nz + j for u_z = 1 (sim_koopman_set_bilinear's Hhat is H with that permutation
+   undone).  With H_c (nz x nz) the block of H that multiplies u_c z, the step is A z + B u + sum_c
+   H_c (u_c z), its adjoint dH_c += lambda_{i+1} (u_c z^_i)' and lambda_i = g_i + A' lambda_{i+1} +
+   sum_c u_c H_c' lambda_{i+1}; u is data and has no gradient.  The sparsity and spectral-radius terms
+   of H that k_linear_loss computes but leaves out of total_loss are not built either.
+   create_bilinear: SIM_E_ARG for u_z other than 0 or 1; every other refusal as create's. */
 typedef struct sim_koopman_train_opts {
   int32_t struct_size; /* sizeof(sim_koopman_train_opts) */
   int32_t abi_version; /* SIM_ABI_VERSION */
@@ -177,6 +193,9 @@ typedef struct sim_koopman_trainer sim_koopman_trainer;
 int sim_koopman_trainer_nparam(const sim_koopman_desc* desc);
 int sim_koopman_trainer_create(const sim_koopman_desc* desc, const double* params, int max_batch,
                                const sim_koopman_train_opts* opts, int device, sim_koopman_trainer** out);
+int sim_koopman_trainer_nparam_bilinear(const sim_koopman_desc* desc);
+int sim_koopman_trainer_create_bilinear(const sim_koopman_desc* desc, const double* params, int u_z, int max_batch,
+                                        const sim_koopman_train_opts* opts, int device, sim_koopman_trainer** out);
 void sim_koopman_trainer_free(sim_koopman_trainer* tr);
 int sim_koopman_trainer_get_params(sim_koopman_trainer* tr, double* host_params);
 int sim_koopman_trainer_set_params(sim_koopman_trainer* tr, const double* host_params, int reset_optimizer);

@@ -163,6 +163,7 @@ EXPORTS = [
     "sim_koopman_trainer_nparam", "sim_koopman_trainer_create", "sim_koopman_trainer_free",
     "sim_koopman_trainer_get_params", "sim_koopman_trainer_set_params",
     "sim_koopman_loss_grad", "sim_koopman_train_step",
+    "sim_koopman_trainer_nparam_bilinear", "sim_koopman_trainer_create_bilinear",
 ]
 PROF_KINDS = ["step_fused", "collide", "substep", "geom"]
 
@@ -218,6 +219,9 @@ def load_lib(path=None):
     lib.sim_koopman_trainer_nparam.argtypes = [C.POINTER(KoopmanDesc)]
     lib.sim_koopman_trainer_create.argtypes = [C.POINTER(KoopmanDesc), vp, ip, C.POINTER(KoopmanTrainOpts), ip,
                                                C.POINTER(vp)]
+    lib.sim_koopman_trainer_nparam_bilinear.argtypes = [C.POINTER(KoopmanDesc)]
+    lib.sim_koopman_trainer_create_bilinear.argtypes = [C.POINTER(KoopmanDesc), vp, ip, ip, C.POINTER(KoopmanTrainOpts), ip,
+                                                        C.POINTER(vp)]
     lib.sim_koopman_trainer_free.argtypes = [vp]
     lib.sim_koopman_trainer_free.restype = None
     lib.sim_koopman_trainer_get_params.argtypes = [vp, vp]

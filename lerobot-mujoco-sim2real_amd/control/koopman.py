@@ -5,7 +5,7 @@ Reference: ``models/KoopmanBase.py:12-60`` (``Koopmanlinear``, the ``DKUC`` mode
 64, 24]`` (``args.py:103``), so ``Nkoopman = 24 + x_dim = 32``.  Only what the controller needs
 is kept: the encoder ``x_encoder(x) = cat([x, MLP(x)])``, the Koopman matrices ``lA``
 (Nkoopman x Nkoopman, initialised as 0.9 x an orthogonalised Gaussian draw) and ``lB``
-(Nkoopman x u_dim), and the fixed decoder ``lC = [I | 0]``.  Training the DKUC model (``train.py``,
+(Nkoopman x u_dim), and the fixed decoder ``lC = [I | 0]``.  Training either model (``train.py``,
 ``models/losses.py``) is ``control/koopman_train.py`` (the fused device step); its evaluation -- the
 multi-step open-loop prediction error of ``evaluate()`` -- is :func:`open_loop_prediction` /
 :func:`prediction_errors` here and ``MPCController.predict`` / ``evaluate`` on the device.  Parameter names are the reference's

@@ -1,4 +1,4 @@
-"""Training the DKUC Koopman model on the device: the fused loss / gradient / Adam step.
+"""Training the DKUC and DBKN Koopman models on the device: the fused loss / gradient / Adam step.
 
 Reference: ``train()`` (``train.py:89-266``) over ``k_linear_loss`` (``models/losses.py:54-129``,
 ``loss_name = "mse"``) with ``torch.optim.Adam`` and ``ExponentialLR(0.99)``.  One step there is six
@@ -8,15 +8,19 @@ and the optimizer; here it is two kernel launches (``include/koopman_mpc.h``
 
 * :class:`KoopmanTrainer` -- the device trainer of one ``Koopmanlinear``: :meth:`loss_grad`,
   :meth:`step`, :meth:`get_params` / :meth:`set_params`, :meth:`to_net`;
+* :class:`BilinearKoopmanTrainer` -- the same for one ``KoopmanBlinear`` (DBKN: the step gains
+  ``H vec(z ⊗ u)``, the reference's ``koopman_operation``, ``models/KoopmanBase.py:62-78``);
 * :func:`params_from_net` / :func:`params_to_net` -- the flat parameter vector
-  ``[W_0 | b_0 | ... | A | B]`` of a net and back;
+  ``[W_0 | b_0 | ... | A | B]`` (``| H`` for DBKN) of a net and back;
 * :func:`schedule` / :func:`train` -- the reference's loop: shuffled minibatches from a seeded
   generator, a window start drawn per step, ``lr * 0.99^epoch``, ``MPCController.evaluate`` every
-  ``eval_interval`` epochs, the best parameters kept.
+  ``eval_interval`` epochs, the best parameters kept; the trainer is picked by the net's type.
 
-Built: DKUC with the ``mse`` loss.  The bilinear DBKN (``net.H``), the DKN / DKAC input encoders,
-the other loss names and the two regularisers ``k_linear_loss`` leaves out of ``total_loss`` are
-refused, not ignored.  There is no CPU path.
+Built: DKUC and the bilinear DBKN (``net.H``, both ``u_z`` orders) with the ``mse`` loss.  The DKN /
+DKAC input encoders, the other loss names and the two regularisers ``k_linear_loss`` leaves out of
+``total_loss`` (DBKN's ``‖H‖₁`` among them) are refused, not ignored.  :class:`KoopmanTrainer` itself
+still refuses a net with ``H``: a DBKN net trained as DKUC would silently lose its bilinear term.
+There is no CPU path.
 """
 import ctypes as C
 
@@ -31,13 +35,36 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-def _check_net(net):
+def _has_h(net):
     import torch
 
-    if isinstance(getattr(net, "H", None), torch.nn.Module):
-        raise NotImplementedError("KoopmanTrainer: the bilinear DBKN model (net.H) is not built; DKUC only")
+    return isinstance(getattr(net, "H", None), torch.nn.Module)
+
+
+def _check_net(net):
+    if _has_h(net):
+        raise NotImplementedError("KoopmanTrainer: DKUC only; the bilinear DBKN model (net.H) is trained by "
+                                  "BilinearKoopmanTrainer")
+    _check_common(net, "KoopmanTrainer", "DKUC")
+
+
+def _check_bilinear_net(net):
+    from .koopman import KoopmanBlinear
+
+    if not isinstance(net, KoopmanBlinear) or not _has_h(net):
+        raise NotImplementedError("BilinearKoopmanTrainer: the net must be a KoopmanBlinear (DBKN); a Koopmanlinear "
+                                  "is trained by KoopmanTrainer")
+    want = (net.Nkoopman, net.Nkoopman * net.u_dim)
+    if tuple(net.H.weight.shape) != want or net.H.bias is not None:
+        raise ValueError(f"net.H must be Linear({want[1]} -> {want[0]}, bias=False)")
+    _check_common(net, "BilinearKoopmanTrainer", "DBKN")
+
+
+def _check_common(net, who, model):
+    import torch
+
     if not isinstance(getattr(net, "u_encode_net", None), torch.nn.Identity):
-        raise NotImplementedError("KoopmanTrainer: an input encoder (DKN / DKAC) is not built; DKUC only")
+        raise NotImplementedError(f"{who}: an input encoder (DKN / DKAC) is not built; {model} only")
     lC = net.lC.weight.detach().double().cpu().numpy()
     if not np.array_equal(lC, np.eye(net.x_dim, net.Nkoopman)):
         raise ValueError("net.lC.weight must be the frozen decoder [I | 0]")
@@ -45,11 +72,14 @@ def _check_net(net):
 
 def params_from_net(net):
     """The flat float64 parameter vector of a ``Koopmanlinear``:
-    ``[W_0 | b_0 | ... | W_{nl-1} | b_{nl-1} | lA (nz x nz) | lB (nz x u_dim)]``, row-major."""
+    ``[W_0 | b_0 | ... | W_{nl-1} | b_{nl-1} | lA (nz x nz) | lB (nz x u_dim)]``, row-major; a
+    ``KoopmanBlinear``'s ends with ``H (nz x nz u_dim)``, ``net.H.weight`` in the net's own ``u_z`` order."""
     parts = []
     for W, b in net.encoder_layers():
         parts += [W.ravel(), b]
     parts += [net.lA.weight.detach().double().cpu().numpy().ravel(), net.lB.weight.detach().double().cpu().numpy().ravel()]
+    if _has_h(net):
+        parts.append(net.H.weight.detach().double().cpu().numpy().ravel())
     return np.ascontiguousarray(np.concatenate(parts), np.float64)
 
 
@@ -59,12 +89,13 @@ def params_to_net(params, net):
 
     p = np.asarray(params, np.float64).ravel()
     mods = [m for m in net.x_encode_net if isinstance(m, torch.nn.Linear)]
-    want = sum(m.weight.numel() + m.bias.numel() for m in mods) + net.lA.weight.numel() + net.lB.weight.numel()
+    tail = [net.lA.weight, net.lB.weight] + ([net.H.weight] if _has_h(net) else [])
+    want = sum(m.weight.numel() + m.bias.numel() for m in mods) + sum(t.numel() for t in tail)
     if p.size != want:
         raise ValueError(f"params_to_net: {p.size} parameters given, the net has {want}")
     o = 0
     with torch.no_grad():
-        for t in [x for m in mods for x in (m.weight, m.bias)] + [net.lA.weight, net.lB.weight]:
+        for t in [x for m in mods for x in (m.weight, m.bias)] + tail:
             k = t.numel()
             t.copy_(torch.as_tensor(p[o:o + k].reshape(tuple(t.shape)), dtype=t.dtype))
             o += k
@@ -79,15 +110,25 @@ class KoopmanTrainer:
     ``pre_length``, ``npos``, ``gamma`` as the reference's args (5, 3, 0.8); ``betas``, ``eps``
     Adam's.  ``loss_name`` must be ``"mse"``."""
 
+    _check = staticmethod(_check_net)
+
+    def _nparam(self, d):
+        return self.lib.sim_koopman_trainer_nparam(C.byref(d))
+
+    def _create(self, d, p, max_batch, o, device):
+        return self.lib.sim_koopman_trainer_create(C.byref(d), p.ctypes.data_as(C.c_void_p), int(max_batch), C.byref(o),
+                                                   device, C.byref(self._h))
+
     def __init__(self, net, max_batch, device=0, pre_length=5, npos=3, gamma=0.8, betas=(0.9, 0.999), eps=1e-8,
                  loss_name="mse"):
         import torch
 
         if loss_name != "mse":
-            raise NotImplementedError(f"KoopmanTrainer: loss_name {loss_name!r} is not built; 'mse' only")
-        _check_net(net)
+            raise NotImplementedError(f"{type(self).__name__}: loss_name {loss_name!r} is not built; 'mse' only")
+        self._h = None
+        self._check(net)
         if not torch.cuda.is_available():
-            raise RuntimeError("KoopmanTrainer needs a ROCm GPU (torch.cuda.is_available() is False)")
+            raise RuntimeError(f"{type(self).__name__} needs a ROCm GPU (torch.cuda.is_available() is False)")
         self.torch, self.net = torch, net
         self.device = torch.device("cuda", device)
         self.x_dim, self.u_dim, self.pre_length = net.x_dim, net.u_dim, int(pre_length)
@@ -102,15 +143,14 @@ class KoopmanTrainer:
         o.beta1, o.beta2, o.eps = float(betas[0]), float(betas[1]), float(eps)
         self.lib = abi.load_lib()
         p = params_from_net(net)
-        n = self.lib.sim_koopman_trainer_nparam(C.byref(d))
+        n = self._nparam(d)
         if n < 0:
             abi.check(self.lib, n)
         if n != p.size:
-            raise ValueError(f"KoopmanTrainer: the net has {p.size} parameters, the library expects {n}")
+            raise ValueError(f"{type(self).__name__}: the net has {p.size} parameters, the library expects {n}")
         self.nparam, self.max_batch = n, int(max_batch)
         self._h = C.c_void_p()
-        abi.check(self.lib, self.lib.sim_koopman_trainer_create(C.byref(d), p.ctypes.data_as(C.c_void_p), int(max_batch),
-                                                                C.byref(o), device, C.byref(self._h)))
+        abi.check(self.lib, self._create(d, p, max_batch, o, device))
 
     def __del__(self):
         try:
@@ -179,6 +219,21 @@ class KoopmanTrainer:
         return params_to_net(self.get_params() if params is None else params, self.net if net is None else net)
 
 
+class BilinearKoopmanTrainer(KoopmanTrainer):
+    """The device trainer of one DBKN model: a ``KoopmanBlinear`` (either ``u_z``) with the identity
+    input encoder and the frozen ``lC``.  The methods are :class:`KoopmanTrainer`'s; the parameter
+    vector ends with ``H`` (:func:`params_from_net`)."""
+
+    _check = staticmethod(_check_bilinear_net)
+
+    def _nparam(self, d):
+        return self.lib.sim_koopman_trainer_nparam_bilinear(C.byref(d))
+
+    def _create(self, d, p, max_batch, o, device):
+        return self.lib.sim_koopman_trainer_create_bilinear(C.byref(d), p.ctypes.data_as(C.c_void_p), int(bool(self.net.u_z)),
+                                                            int(max_batch), C.byref(o), device, C.byref(self._h))
+
+
 def schedule(seed, n_traj, steps, pre_length, batch_size, epochs):
     """The minibatches and window starts of :func:`train`, a pure function of its arguments:
     a list over epochs of lists of (idx int32 numpy, t0); every epoch a fresh permutation of the
@@ -220,7 +275,8 @@ def train(net, rollout, args=None, epochs=10, batch_size=128, lr=1e-3, lr_decay=
     r = torch.as_tensor(rollout).to(device=dev, dtype=torch.float32).contiguous()
     ev = r if eval_rollout is None else torch.as_tensor(eval_rollout).to(device=dev, dtype=torch.float32).contiguous()
     T, N = r.shape[0] - 1, r.shape[1]
-    tr = KoopmanTrainer(net, min(batch_size, N), device=device, pre_length=pre_length, npos=npos, gamma=gamma)
+    cls = BilinearKoopmanTrainer if _has_h(net) else KoopmanTrainer  # DBKN / DKUC
+    tr = cls(net, min(batch_size, N), device=device, pre_length=pre_length, npos=npos, gamma=gamma)
     sched = schedule(seed, N, T, pre_length, batch_size, epochs)
     hist = dict(train_loss=[], lr=[], eval=[], best_epoch=-1, best_error=float("inf"), best_params=tr.get_params())
     for ep, batches in enumerate(sched):

@@ -1,5 +1,6 @@
-// koopman_train.hip — one training step of the DKUC Koopman model (include/koopman_mpc.h
-// sim_koopman_trainer_*, sim_koopman_loss_grad, sim_koopman_train_step) on float64 MFMA.
+// koopman_train.hip — one training step of the DKUC Koopman model and of the bilinear DBKN one
+// (include/koopman_mpc.h sim_koopman_trainer_*, sim_koopman_loss_grad, sim_koopman_train_step) on
+// float64 MFMA.
 //
 // Reference: train() (train.py:89-266) over k_linear_loss (models/losses.py:54-129, "mse") and
 // torch.optim.Adam: per step six encoder calls, five lA / lB steps, about fifteen MSE reductions,
@@ -228,7 +229,13 @@ DEVI void encode_backward(const KDev& K, const TDev& D, const double* blob, doub
 // (blob, ws and scratch are not __restrict__: the fragment loads of [A | B], A' and the last layer's W'
 // are invariant across the steps, and with the promise that the slot's stores do not alias them the
 // compiler keeps all of them in registers across the loop -- 200 VGPRs at four feature tiles, and spills)
-template <int NTL>
+//
+// BIL: the bilinear DBKN step z^_{i+1} = A z^_i + B u_i + sum_c H_c (u_{i,c} z^_i), c < u_dim.  Its blocks
+// follow the linear ones (koopman_train_plan.h): the H_c fragments [ud][NZT][ATKS][64] right after A',
+// then the H_c' ones; dH_c's tiles [ud][NZT][NZT] right after [dA | dB] in the slot.  u_c of the lane's
+// sample is a scalar on the N side, so it scales the B operand (forward), the transposed z^ tiles
+// (dH_c = lambda_{i+1} (u_c z^_i)') and the C/D output (u_c H_c' lambda_{i+1}); c is a runtime loop.
+template <int NTL, bool BIL>
 __global__ __launch_bounds__(256) void k_koopman_grad(KDev K, TDev D, const double* blob, int n, int N,
                                                        const float* __restrict__ rows, int ld, int x_off, int u_off,
                                                        const int* __restrict__ traj_idx, int t0,
@@ -302,6 +309,32 @@ __global__ __launch_bounds__(256) void k_koopman_grad(KDev K, TDev D, const doub
         for (int q = 0; q < NZT; q++) zn[q] = mfma(w[j][q], b, zn[q]);
       }
       sched_fence();
+    }
+    if constexpr (BIL) {  // + sum_c H_c (u_c z^_i): A's k-loop per c, the B operand scaled by the sample's u_c
+      for (int c = 0; c < K.ud; c++) {
+        // ub is in the B layout: u_c sits in register c >> 2 of the lane with kq = c & 3 and this column
+        const double uc = __shfl(c < 4 ? ub[0] : ub[1], (c & 3) * 16 + col);
+        const double* HF = opaque(blob + D.at + (size_t)(1 + c) * (NZT * ATKS * 64) + lane);
+        double sz[ATKS];
+        sz[0] = uc * zx[0], sz[1] = uc * zx[1];
+#pragma unroll
+        for (int q = 0; q < NTL; q++)
+#pragma unroll
+          for (int r = 0; r < 4; r++) sz[2 + 4 * q + r] = uc * zf[q][r];
+#pragma unroll
+        for (int s0 = 0; s0 < ATKS; s0 += 2) {  // (ATKS is even) 2 NZT fragment loads, then their MFMAs
+          double w[2][NZT];
+#pragma unroll
+          for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int q = 0; q < NZT; q++) w[j][q] = HF[(q * ATKS + s0 + j) * 64];
+#pragma unroll
+          for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int q = 0; q < NZT; q++) zn[q] = mfma(w[j][q], sz[s0 + j], zn[q]);
+          sched_fence();
+        }
+      }
     }
     // Psi(x_{t0+i+1}), its hidden activations kept for the backward below
     d4 out[KT];
@@ -383,6 +416,32 @@ __global__ __launch_bounds__(256) void k_koopman_grad(KDev K, TDev D, const doub
       }
       sched_fence();
     }
+    if constexpr (BIL) {  // dH_c += lambda_{i+1} (u_c z^_i)': dA's products, the transposed z^ tiles scaled
+      for (int c = 0; c < K.ud; c++) {
+        double* sH = opaque(slot + D.sA + NZT * (NZT + 1) * 256 + c * (NZT * NZT * 256) + lane);
+        double tS[NZT][4];
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+          // the transposed u tile's row c: u_c of sample 4 s + kq sits in the lane of that kq with column c
+          const double us = __shfl(tB[NZT][s], kq * 16 + c);
+#pragma unroll
+          for (int q = 0; q < NZT; q++) tS[q][s] = us * tB[q][s];
+        }
+        sched_fence();
+#pragma unroll
+        for (int Tr = 0; Tr < NZT; Tr++) {
+#pragma unroll
+          for (int Tc = 0; Tc < NZT; Tc++) {
+            d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int s = 0; s < 4; s++) acc = mfma(tA[Tr][s], tS[Tc][s], acc);
+#pragma unroll
+            for (int r = 0; r < 4; r++) accum(sH + ((Tr * NZT + Tc) * 4 + r) * 64, acc[r], first);
+          }
+          sched_fence();
+        }
+      }
+    }
     d4 ln[NZT];
 #pragma unroll
     for (int q = 0; q < NZT; q++) ln[q] = d4{0.0, 0.0, 0.0, 0.0};
@@ -401,6 +460,33 @@ __global__ __launch_bounds__(256) void k_koopman_grad(KDev K, TDev D, const doub
         for (int q = 0; q < NZT; q++) ln[q] = mfma(w[j][q], b, ln[q]);
       }
       sched_fence();
+    }
+    if constexpr (BIL) {  // + sum_c u_c (H_c' lambda_{i+1}): A's loop into a fresh accumulator, its output scaled
+      for (int c = 0; c < K.ud; c++) {
+        const double uc = __shfl(c < 4 ? ub[0] : ub[1], (c & 3) * 16 + col);
+        const double* HT = opaque(blob + D.at + (size_t)(1 + K.ud + c) * (NZT * ATKS * 64) + lane);
+        d4 lh[NZT];
+#pragma unroll
+        for (int q = 0; q < NZT; q++) lh[q] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s0 = 0; s0 < ATKS; s0 += 2) {
+          double w[2][NZT];
+#pragma unroll
+          for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int q = 0; q < NZT; q++) w[j][q] = HT[(q * ATKS + s0 + j) * 64];
+#pragma unroll
+          for (int j = 0; j < 2; j++) {
+            const int s = s0 + j;
+            const double b = s < 2 ? lx[s] : lf[(s - 2) >> 2][(s - 2) & 3];
+#pragma unroll
+            for (int q = 0; q < NZT; q++) lh[q] = mfma(w[j][q], b, lh[q]);
+          }
+          sched_fence();
+        }
+#pragma unroll
+        for (int q = 0; q < NZT; q++) ln[q] += uc * lh[q];
+      }
     }
     if (i > 0) {  // + g_i
       const double* sg = opaque(scr + ((size_t)(i - 1) * 2 + 1) * NZT * 256);
@@ -487,7 +573,9 @@ __global__ __launch_bounds__(256) void k_koopman_apply(ADev a) {
 
 typedef void (*GradFn)(KDev, TDev, const double*, int, int, const float*, int, int, int, const int*, int, double*,
                        double*, int*, int);
-const GradFn GRAD[4] = {k_koopman_grad<1>, k_koopman_grad<2>, k_koopman_grad<3>, k_koopman_grad<4>};
+const GradFn GRAD[2][4] = {
+    {k_koopman_grad<1, false>, k_koopman_grad<2, false>, k_koopman_grad<3, false>, k_koopman_grad<4, false>},
+    {k_koopman_grad<1, true>, k_koopman_grad<2, true>, k_koopman_grad<3, true>, k_koopman_grad<4, true>}};
 
 }  // namespace
 
@@ -535,7 +623,7 @@ int launch(sim_koopman_trainer* t, int n, int N, int T, const float* rows, int l
   if (n == 0) return SIM_OK;
   const ktrain::Plan& pl = t->pl;
   const int waves = (n + 15) / 16;
-  hipLaunchKernelGGL(GRAD[pl.ntl - 1], dim3((waves + ktrain::WAVES - 1) / ktrain::WAVES), dim3(64 * ktrain::WAVES),
+  hipLaunchKernelGGL(GRAD[pl.bil][pl.ntl - 1], dim3((waves + ktrain::WAVES - 1) / ktrain::WAVES), dim3(64 * ktrain::WAVES),
                      pl.lds_bytes, (hipStream_t)stream, t->kd, t->td, t->d_blob, n, N, rows, ld, x_off, u_off,
                      (const int*)traj_idx, t0, t->d_ws, t->d_scr, t->d_step, update);
   TCHECK(hipGetLastError());
@@ -550,11 +638,7 @@ int launch(sim_koopman_trainer* t, int n, int N, int T, const float* rows, int l
   return SIM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int sim_koopman_trainer_nparam(const sim_koopman_desc* desc) {
+int nparam_of(const sim_koopman_desc* desc, bool bil) {
   if (!desc) return soarm_set_error(SIM_E_ARG, "null argument");
   sim_koopman_train_opts o{};
   o.pre_length = 1, o.npos = 1, o.gamma = 1.0, o.beta1 = 0.9, o.beta2 = 0.999, o.eps = 1e-8;
@@ -563,19 +647,19 @@ int sim_koopman_trainer_nparam(const sim_koopman_desc* desc) {
   std::string err;
   // (the layout does not depend on the options; npos = 1 needs x_dim >= 2, checked by create)
   if (d.x_dim < 2) return soarm_set_error(SIM_E_MODEL, "trainer: x_dim must be >= 2");
-  if (int rc = ktrain::make_plan(d, o, pl, err)) return soarm_set_error(rc, err);
+  if (int rc = ktrain::make_plan(d, o, pl, err, bil, 0)) return soarm_set_error(rc, err);
   return pl.nparam;
 }
 
-int sim_koopman_trainer_create(const sim_koopman_desc* desc, const double* params, int max_batch,
-                               const sim_koopman_train_opts* opts, int device, sim_koopman_trainer** out) {
+int create(const sim_koopman_desc* desc, const double* params, bool bil, int u_z, int max_batch,
+           const sim_koopman_train_opts* opts, int device, sim_koopman_trainer** out) {
   if (!desc || !params || !opts || !out) return soarm_set_error(SIM_E_ARG, "null argument");
   *out = nullptr;
   if (int rc = check_struct(opts, "sim_koopman_train_opts")) return rc;
   if (max_batch < 1) return soarm_set_error(SIM_E_ARG, "trainer: max_batch must be >= 1");
   ktrain::Plan pl;
   std::string err;
-  if (int rc = ktrain::make_plan(*desc, *opts, pl, err)) return soarm_set_error(rc, err);
+  if (int rc = ktrain::make_plan(*desc, *opts, pl, err, bil, u_z)) return soarm_set_error(rc, err);
   std::vector<int32_t> map, gidx;
   if (!ktrain::index_map(pl, map) || !ktrain::grad_index(pl, gidx))
     return soarm_set_error(SIM_E_MODEL, "trainer: inconsistent index map");
@@ -612,7 +696,7 @@ int sim_koopman_trainer_create(const sim_koopman_desc* desc, const double* param
     rc = soarm_set_error(SIM_E_HIP, "hipMemcpy failed");
   if (!rc && hipMemcpy(t->d_gidx, gidx.data(), gidx.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
     rc = soarm_set_error(SIM_E_HIP, "hipMemcpy failed");
-  if (!rc && hipFuncSetAttribute((const void*)GRAD[pl.ntl - 1], hipFuncAttributeMaxDynamicSharedMemorySize,
+  if (!rc && hipFuncSetAttribute((const void*)GRAD[pl.bil][pl.ntl - 1], hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)ktrain::LDS_BYTES) != hipSuccess)
     rc = soarm_set_error(SIM_E_HIP, "hipFuncSetAttribute failed");
   if (rc) {
@@ -621,6 +705,23 @@ int sim_koopman_trainer_create(const sim_koopman_desc* desc, const double* param
   }
   *out = t;
   return SIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sim_koopman_trainer_nparam(const sim_koopman_desc* desc) { return nparam_of(desc, false); }
+int sim_koopman_trainer_nparam_bilinear(const sim_koopman_desc* desc) { return nparam_of(desc, true); }
+
+int sim_koopman_trainer_create(const sim_koopman_desc* desc, const double* params, int max_batch,
+                               const sim_koopman_train_opts* opts, int device, sim_koopman_trainer** out) {
+  return create(desc, params, false, 0, max_batch, opts, device, out);
+}
+
+int sim_koopman_trainer_create_bilinear(const sim_koopman_desc* desc, const double* params, int u_z, int max_batch,
+                                        const sim_koopman_train_opts* opts, int device, sim_koopman_trainer** out) {
+  return create(desc, params, true, u_z, max_batch, opts, device, out);
 }
 
 void sim_koopman_trainer_free(sim_koopman_trainer* t) {

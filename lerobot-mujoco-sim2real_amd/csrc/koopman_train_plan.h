@@ -12,6 +12,15 @@
 //   ab        [A | B]: [1 + ntl][2 + 4 ntl + 2][64], tile 0 = the x rows, tiles 1.. = the features,
 //             k order [x (8) | features (16 ntl) | u (8)] (k_predict's);
 //   at        A': [1 + ntl][2 + 4 ntl][64] over the same tile and k orders.
+// The bilinear plan (DBKN, make_plan(..., bil = true, u_z)) appends one block to each of the three:
+//   parameters  H (nz x nz u_dim row-major, net.H.weight in the net's own u_z order) after B;
+//   blob        hf [u_dim][1 + ntl][2 + 4 ntl][64]: H_c in the tile and k order of the A part of ab,
+//               right after at; then ht, H_c' in at's order.  H_c (nz x nz) is the block of H that
+//               multiplies u_c z: H_c[i][j] = H[i][c nz + j] (u_z = 1) or H[i][j u_dim + c] (u_z = 0)
+//               -- the order is a matter of the index map alone;
+//   slot        sH: dH_c as [u_dim][1 + ntl][1 + ntl] tiles in the C/D layout, right after [dA | dB].
+// The kernel derives the three offsets from at, sA and the shape, so the DKUC plan's numbers and the
+// kernels' argument struct are what they were.
 #ifndef KOOPMAN_TRAIN_PLAN_H
 #define KOOPMAN_TRAIN_PLAN_H
 
@@ -37,13 +46,16 @@ struct Plan {
   int bias, enc_total;                                             // doubles staged in LDS
   int wt[SIM_KMAXLAYER], kst[SIM_KMAXLAYER];                       // W_l' fragments, their k-steps
   int ab, abks, at, atks;
+  int bil, uz;  // the bilinear plan (DBKN) and its H column order; hf, ht, pH, sH are -1 without it
+  int hf, ht;   // H_c, H_c' fragments: [ud][1 + ntl][atks][64] each
   int blob_total;
-  int pw[SIM_KMAXLAYER], pb[SIM_KMAXLAYER], pA, pB, nparam;  // offsets into the parameter vector
+  int pw[SIM_KMAXLAYER], pb[SIM_KMAXLAYER], pA, pB, pH, nparam;  // offsets into the parameter vector
   // a wave's partial-gradient slot: every product's output tiles in the C/D layout, [tile][r][64]
   // (lane l, register r = row (l >> 4) + 4 r, column l & 15 of the tile)
   int sw[SIM_KMAXLAYER];  // dW_l: [ntile[l]][input tiles: 1 (l = 0) or 4]
   int sb[SIM_KMAXLAYER];  // db_l: [64]
   int sA;                 // [dA | dB]: [1 + ntl][1 + ntl + 1], the last tile column = dB
+  int sH;                 // dH_c: [ud][1 + ntl][1 + ntl]
   int slot_stride;   // doubles of a slot: the above + 8 (the loss sums)
   int scr_stride;    // doubles of one wave's scratch: z^ and g [P][2][1 + ntl][4][64], then one
                      // encode's hidden activations [MAXL - 1][4][4][64]
@@ -52,7 +64,8 @@ struct Plan {
 
 // the shape checks of sim_koopman_create, then the trainer's own; fills pl.  SIM_OK or an error
 // code with its message in err
-inline int make_plan(const sim_koopman_desc& d, const sim_koopman_train_opts& o, Plan& pl, std::string& err) {
+inline int make_plan(const sim_koopman_desc& d, const sim_koopman_train_opts& o, Plan& pl, std::string& err,
+                     bool bil = false, int u_z = 0) {
   const int xd = d.x_dim, ud = d.u_dim, nl = d.nlayer;
   if (xd < 1 || xd > SIM_KMAXX) return err = "x_dim must be in 1..8", SIM_E_MODEL;
   if (ud < 1 || ud > SIM_KMAXU) return err = "u_dim must be in 1..8", SIM_E_MODEL;
@@ -69,7 +82,9 @@ inline int make_plan(const sim_koopman_desc& d, const sim_koopman_train_opts& o,
   if (!(o.gamma > 0.0)) return err = "trainer: gamma must be positive", SIM_E_ARG;
   if (!(o.beta1 >= 0.0 && o.beta1 < 1.0) || !(o.beta2 >= 0.0 && o.beta2 < 1.0) || !(o.eps >= 0.0))
     return err = "trainer: beta1, beta2 must be in [0, 1) and eps >= 0", SIM_E_ARG;
+  if (bil && u_z != 0 && u_z != 1) return err = "trainer: u_z must be 0 (vec(z (x) u)) or 1 (vec(u (x) z))", SIM_E_ARG;
   pl = Plan{};
+  pl.bil = bil, pl.uz = bil ? u_z : 0, pl.hf = pl.ht = pl.pH = pl.sH = -1;
   pl.xd = xd, pl.ud = ud, pl.nl = nl, pl.outw = d.width[nl], pl.nz = xd + d.width[nl];
   pl.P = o.pre_length, pl.npos = o.npos;
   for (int l = 0; l <= nl; l++) pl.width[l] = d.width[l];
@@ -92,6 +107,10 @@ inline int make_plan(const sim_koopman_desc& d, const sim_koopman_train_opts& o,
   pl.abks = 2 + 4 * pl.ntl + 2, pl.atks = 2 + 4 * pl.ntl;
   pl.ab = off, off += (1 + pl.ntl) * pl.abks * 64;
   pl.at = off, off += (1 + pl.ntl) * pl.atks * 64;
+  if (bil) {
+    pl.hf = off, off += ud * (1 + pl.ntl) * pl.atks * 64;
+    pl.ht = off, off += ud * (1 + pl.ntl) * pl.atks * 64;
+  }
   pl.blob_total = off;
   int p = 0;
   for (int l = 0; l < nl; l++) {
@@ -100,6 +119,7 @@ inline int make_plan(const sim_koopman_desc& d, const sim_koopman_train_opts& o,
   }
   pl.pA = p, p += pl.nz * pl.nz;
   pl.pB = p, p += pl.nz * ud;
+  if (bil) pl.pH = p, p += pl.nz * pl.nz * ud;
   pl.nparam = p;
   int so = 0;
   for (int l = 0; l < nl; l++) {
@@ -107,6 +127,7 @@ inline int make_plan(const sim_koopman_desc& d, const sim_koopman_train_opts& o,
     pl.sb[l] = so, so += 64;
   }
   pl.sA = so, so += (1 + pl.ntl) * (2 + pl.ntl) * 256;
+  if (bil) pl.sH = so, so += ud * (1 + pl.ntl) * (1 + pl.ntl) * 256;
   pl.slot_stride = so + 8;
   pl.scr_stride = pl.P * 2 * (1 + pl.ntl) * 4 * 64 + (MAXL - 1) * 4 * 4 * 64;
   pl.lds_bytes = ((size_t)pl.enc_total + (size_t)WAVES * 16 * TILE_LD) * sizeof(double);
@@ -127,6 +148,11 @@ inline int z_of_k(const Plan& pl, int kk) {
   if (kk < 8) return kk < pl.xd ? kk : -1;
   kk -= 8;
   return (kk < 16 * pl.ntl && kk < pl.outw) ? pl.xd + kk : -1;
+}
+
+// parameter index of H_c[i][j] (bilinear plan)
+inline int h_param(const Plan& pl, int c, int i, int j) {
+  return pl.pH + i * (pl.nz * pl.ud) + (pl.uz ? c * pl.nz + j : j * pl.ud + c);
 }
 
 // map[c][p], c = 0, 1: the blob positions parameter p is copied to (-1 = none).  Every parameter has
@@ -180,6 +206,17 @@ inline bool index_map(const Plan& pl, std::vector<int32_t>& map) {
         if (i >= 0 && j >= 0) put(pl.pA + i * pl.nz + j, pl.at + (tile * pl.atks + s) * 64 + lane);
       }
   }
+  if (pl.bil)  // H_c as A's part of ab, H_c' as at: every H parameter has exactly these two copies
+    for (int c = 0; c < pl.ud; c++)
+      for (int tile = 0; tile <= pl.ntl; tile++)
+        for (int s = 0; s < pl.atks; s++)
+          for (int lane = 0; lane < 64; lane++) {
+            const int r = z_of_row(pl, tile, lane & 15), k = z_of_k(pl, 4 * s + (lane >> 4));
+            if (r < 0 || k < 0) continue;
+            const int o = ((c * (1 + pl.ntl) + tile) * pl.atks + s) * 64 + lane;
+            put(h_param(pl, c, r, k), pl.hf + o);
+            put(h_param(pl, c, k, r), pl.ht + o);
+          }
   for (int p = 0; p < pl.nparam; p++)
     if (map[p] < 0) ok = false;
   return ok;
@@ -208,6 +245,12 @@ inline bool grad_index(const Plan& pl, std::vector<int32_t>& gidx) {
     for (int j = 0; j < pl.nz; j++) gidx[pl.pA + i * pl.nz + j] = slot_pos(pl.sA, nti, z_pad(pl, i), z_pad(pl, j));
     for (int c = 0; c < pl.ud; c++) gidx[pl.pB + i * pl.ud + c] = slot_pos(pl.sA, nti, z_pad(pl, i), 16 * (1 + pl.ntl) + c);
   }
+  if (pl.bil)
+    for (int c = 0; c < pl.ud; c++)
+      for (int i = 0; i < pl.nz; i++)
+        for (int j = 0; j < pl.nz; j++)
+          gidx[h_param(pl, c, i, j)] =
+              slot_pos(pl.sH + c * (1 + pl.ntl) * (1 + pl.ntl) * 256, 1 + pl.ntl, z_pad(pl, i), z_pad(pl, j));
   std::vector<uint8_t> used((size_t)pl.slot_stride, 0);
   for (int p = 0; p < pl.nparam; p++) {
     if (gidx[p] < 0 || gidx[p] >= pl.slot_stride - 8 || used[gidx[p]]) return false;

@@ -2,13 +2,16 @@
 """Time the fused Koopman training step (sim_koopman_train_step) against the eager torch step it
 replaces, and run a short train() on a rollout of the project's own generator.
 
-    python tools/bench_koopman_train.py [--batches 128,4096] [--steps 200] [--windows 7]
+    python tools/bench_koopman_train.py [--model DKUC|DBKN] [--batches 128,4096] [--steps 200] [--windows 7]
                                         [--epochs 20] [--out profiles/koopman_train.json]
 
 Needs a GPU.  Per batch size, on a random [T+1, N, 13] fp32 rollout (T = 20):
 
-* fused: `KoopmanTrainer.step` (two launches, no host synchronisation between steps);
-* eager: this project's `Koopmanlinear().double()` on the same GPU, the section-2 loss of
+* fused: `KoopmanTrainer.step` (two launches, no host synchronisation between steps); with
+  `--model DBKN` `BilinearKoopmanTrainer.step` on a `KoopmanBlinear` whose `H` is 0.05 randn (a zero `H`
+  would time the bilinear products on zeros and let the agreement check pass without them), and the
+  default --out is profiles/koopman_train_dbkn.json;
+* eager: this project's `Koopmanlinear().double()` (`KoopmanBlinear` for DBKN) on the same GPU, the section-2 loss of
   include/koopman_mpc.h written with torch ops (six encoder calls, P model steps, the MSE
   reductions), `loss.backward()` and `torch.optim.Adam.step()` -- the parent has no HIP path for
   this step, so this is what a user would run;
@@ -42,11 +45,17 @@ class _Args:
     x_dim, u_dim, MPC_type, layers, model = XD, UD, "delta_mpc", LAYERS, "DKUC"
 
 
-def make_net(seed=0):
+def make_net(seed=0, model="DKUC", hscale=0.05):
     import torch
-    from lerobot_mujoco_sim2real_amd.control.koopman import Koopmanlinear
+    from lerobot_mujoco_sim2real_amd.control.koopman import KoopmanBlinear, Koopmanlinear
     torch.manual_seed(seed)
-    return Koopmanlinear(XD, UD, LAYERS).double()
+    if model == "DKUC":
+        return Koopmanlinear(XD, UD, LAYERS).double()
+    net = KoopmanBlinear(XD, UD, LAYERS).double()
+    with torch.no_grad():  # (H is zero-initialised: hscale = 0 keeps the reference's start)
+        net.H.weight.copy_(hscale * torch.randn(net.H.weight.shape, generator=torch.Generator().manual_seed(seed + 100),
+                                                dtype=torch.float64))
+    return net
 
 
 def eager_loss(net, rows, idx, t0):
@@ -63,19 +72,19 @@ def eager_loss(net, rows, idx, t0):
     return (koop + pred) / sum(beta)
 
 
-def bench_batch(n, steps, windows):
+def bench_batch(n, steps, windows, model="DKUC"):
     import numpy as np
     import torch
-    from lerobot_mujoco_sim2real_amd.control.koopman_train import KoopmanTrainer, params_from_net
+    from lerobot_mujoco_sim2real_amd.control.koopman_train import BilinearKoopmanTrainer, KoopmanTrainer, params_from_net
     dev = torch.device("cuda", 0)
     g = torch.Generator().manual_seed(1)
     rows = (torch.rand((T + 1, n, XD + UD), generator=g) - 0.5).to(dev)
     idx = torch.randperm(n, generator=g).to(dev)
     idx32 = idx.to(torch.int32)
     t0s = [int(v) for v in torch.randint(0, T - P, (steps,), generator=g)]
-    net = make_net().to(dev)
+    net = make_net(model=model).to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=1e-3)
-    tr = KoopmanTrainer(make_net(), n, pre_length=P, gamma=GAMMA)
+    tr = (KoopmanTrainer if model == "DKUC" else BilinearKoopmanTrainer)(make_net(model=model), n, pre_length=P, gamma=GAMMA)
     losses = torch.empty(6, dtype=torch.float64, device=dev)
 
     def eager(k):
@@ -113,7 +122,7 @@ def bench_batch(n, steps, windows):
     return rec
 
 
-def sanity_train(epochs):
+def sanity_train(epochs, model="DKUC"):
     import torch
     from lerobot_mujoco_sim2real_amd import mjcf
     from lerobot_mujoco_sim2real_amd.args import Args
@@ -123,7 +132,7 @@ def sanity_train(epochs):
     gen = SOARM101DataGenerator(Args([]), model=mjcf.compile_mjcf(mjcf.SCENE_XML, disable_contact=True))
     data = gen.rollout_device(n=512, steps=50, input_type="random", seed=1)
     held = gen.rollout_device(n=128, steps=50, input_type="random", seed=2)
-    net = make_net(7)
+    net = make_net(7, model, hscale=0.0)
     before = MPCController(net, _Args).evaluate(held)
     torch.cuda.synchronize()
     a = time.perf_counter()
@@ -144,19 +153,24 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--epochs", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "koopman_train.json"))
+    ap.add_argument("--model", choices=("DKUC", "DBKN"), default="DKUC")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "koopman_train.json" if a.model == "DKUC" else "koopman_train_dbkn.json")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_koopman_train needs a GPU")
     out = dict(device=torch.cuda.get_device_name(0), layers=LAYERS, pre_length=P,
-               step=[bench_batch(int(b), a.steps, a.windows) for b in a.batches.split(",")])
+               step=[bench_batch(int(b), a.steps, a.windows, a.model) for b in a.batches.split(",")])
+    if a.model != "DKUC":
+        out["model"] = a.model
     for r in out["step"]:
         print(f"batch {r['batch']}: fused {r['fused_ms_per_step']:.4f} ms/step ({r['fused_ms_min']:.4f}..{r['fused_ms_max']:.4f}), "
               f"eager {r['eager_ms_per_step']:.4f} ms/step ({r['eager_ms_min']:.4f}..{r['eager_ms_max']:.4f}), "
               f"ratio {r['eager_over_fused']:.1f}x, agree {r['agree_after_3_steps']:.1e}", flush=True)
     if a.epochs > 0:
-        out["train"] = s = sanity_train(a.epochs)
+        out["train"] = s = sanity_train(a.epochs, a.model)
         print(f"train(): {s['epochs']} epochs in {s['wall_s']:.2f} s, loss {s['first_epoch_loss']:.4e} -> {s['last_epoch_loss']:.4e}, "
               f"evaluate avg_error {s['before']['avg_error']:.4f} -> {s['after']['avg_error']:.4f}", flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -1,11 +1,13 @@
 // koopman_train_selftest.cpp — the Koopman trainer's host-side code (csrc/koopman_train_plan.h: the
-// plan, the fragment index map, the slot gather index, blob packing, the per-step argument checks)
-// as a stand-alone program for the host sanitizers.  No GPU, no HIP:
+// plan of the DKUC trainer and of the bilinear DBKN one, the fragment index map, the slot gather index,
+// blob packing, the per-step argument checks) as a stand-alone program for the host sanitizers.  No
+// GPU, no HIP:
 //
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all
 //       tools/koopman_train_selftest.cpp -o /tmp/koopman_train_selftest && /tmp/koopman_train_selftest
 //
 // Prints "selftest ok" and exits 0; any mismatch aborts with a message.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <numeric>
@@ -109,8 +111,84 @@ static void check_shape(std::vector<int> w, int ud, int P) {
   REQUIRE(check_step_args(pl, 32, 16, 0, T, &rows, 13, 5, 0, true, 0, err) == SIM_E_ARG);
 }
 
+// the bilinear plan (DBKN): the linear plan's numbers unmoved, the H block of the parameter vector, the
+// H_c / H_c' fragments against the packing rule restated, dH's slot, the maps one-to-one and in range
+static void check_bilinear(std::vector<int> w, int ud, int P, int u_z) {
+  using namespace ktrain;
+  const sim_koopman_desc d = desc_of(w, ud);
+  const sim_koopman_train_opts o = opts_of(P, 1);
+  Plan lin, pl;
+  std::string err;
+  REQUIRE(make_plan(d, o, lin, err) == SIM_OK);
+  REQUIRE(make_plan(d, o, pl, err, true, u_z) == SIM_OK);
+  REQUIRE(!lin.bil && lin.hf == -1 && lin.ht == -1 && lin.pH == -1 && lin.sH == -1);
+  const int nl = pl.nl, xd = w[0], outw = w[nl], nz = xd + outw, ntl = pl.ntl, nzt = 1 + ntl, atks = pl.atks;
+  // the linear part is where the linear plan has it; the new blocks follow it
+  REQUIRE(pl.bil == 1 && pl.uz == u_z && pl.ab == lin.ab && pl.at == lin.at && pl.pA == lin.pA && pl.pB == lin.pB);
+  REQUIRE(pl.sA == lin.sA && pl.scr_stride == lin.scr_stride && pl.lds_bytes == lin.lds_bytes && pl.enc_total == lin.enc_total);
+  for (int l = 0; l < nl; l++) REQUIRE(pl.pw[l] == lin.pw[l] && pl.sw[l] == lin.sw[l] && pl.frag[l] == lin.frag[l]);
+  REQUIRE(pl.pH == lin.nparam && pl.nparam == lin.nparam + nz * nz * ud);
+  REQUIRE(pl.hf == lin.blob_total && pl.hf == pl.at + nzt * atks * 64);  // (the kernel derives hf, ht, sH so)
+  REQUIRE(pl.ht == pl.hf + ud * nzt * atks * 64 && pl.blob_total == pl.ht + ud * nzt * atks * 64);
+  REQUIRE(pl.sH == pl.sA + nzt * (nzt + 1) * 256 && pl.sH == lin.slot_stride - 8);
+  REQUIRE(pl.slot_stride == pl.sH + ud * nzt * nzt * 256 + 8);
+  std::vector<int32_t> map, gidx, lmap, lgidx;
+  REQUIRE(index_map(pl, map) && grad_index(pl, gidx));
+  REQUIRE(index_map(lin, lmap) && grad_index(lin, lgidx));
+  REQUIRE((int)map.size() == 2 * pl.nparam && (int)gidx.size() == pl.nparam);
+  for (int p = 0; p < lin.nparam; p++)
+    REQUIRE(map[p] == lmap[p] && map[pl.nparam + p] == lmap[lin.nparam + p] && gidx[p] == lgidx[p]);
+  // every H parameter: exactly two copies, one in hf and one in ht; its gradient inside dH's region
+  std::vector<char> seen(pl.slot_stride, 0);
+  for (int p = pl.pH; p < pl.nparam; p++) {
+    const int a = std::min(map[p], map[pl.nparam + p]), b = std::max(map[p], map[pl.nparam + p]);
+    REQUIRE(a >= pl.hf && a < pl.ht && b >= pl.ht && b < pl.blob_total);
+    REQUIRE(gidx[p] >= pl.sH && gidx[p] < pl.slot_stride - 8 && !seen[gidx[p]]);
+    seen[gidx[p]] = 1;
+  }
+  std::vector<double> p(pl.nparam), blob;
+  std::iota(p.begin(), p.end(), 1.0);
+  pack_blob(pl, map, p.data(), blob);
+  REQUIRE((int)blob.size() == pl.blob_total);
+  auto zrow = [&](int tile, int r) { return tile == 0 ? (r < xd ? r : -1) : (16 * (tile - 1) + r < outw ? xd + 16 * (tile - 1) + r : -1); };
+  auto zk = [&](int kk) { return kk < 8 ? (kk < xd ? kk : -1) : (kk - 8 < 16 * ntl && kk - 8 < outw ? xd + kk - 8 : -1); };
+  // H_c[i][j], the factor of u_c z_j in row i, from net.H.weight (nz x nz ud row-major) in the u_z order
+  auto Hc = [&](int c, int i, int j) { return p[pl.pH + i * nz * ud + (u_z ? c * nz + j : j * ud + c)]; };
+  for (int c = 0; c < ud; c++)
+    for (int tile = 0; tile < nzt; tile++)
+      for (int s = 0; s < atks; s++)
+        for (int lane = 0; lane < 64; lane++) {
+          const int r = zrow(tile, lane & 15), k = zk(4 * s + (lane >> 4));
+          const int o2 = ((c * nzt + tile) * atks + s) * 64 + lane;
+          REQUIRE(blob[pl.hf + o2] == ((r >= 0 && k >= 0) ? Hc(c, r, k) : 0.0));
+          REQUIRE(blob[pl.ht + o2] == ((r >= 0 && k >= 0) ? Hc(c, k, r) : 0.0));
+        }
+  // dH_c[i][j] in the slot: tile (row tile of i, column tile of j) of [c][nzt][nzt], C/D layout
+  auto pad = [&](int z) { return z < xd ? z : 16 + (z - xd); };
+  for (int c = 0; c < ud; c++)
+    for (int i = 0; i < nz; i++)
+      for (int j = 0; j < nz; j++) {
+        const int ri = pad(i), cj = pad(j);
+        const int want = pl.sH + (((c * nzt + ri / 16) * nzt + cj / 16) * 4 + (ri % 16) / 4) * 64 + (ri % 4) * 16 + cj % 16;
+        REQUIRE(gidx[pl.pH + i * nz * ud + (u_z ? c * nz + j : j * ud + c)] == want);
+      }
+  // the linear blob is a prefix of the bilinear one
+  std::vector<double> lblob;
+  pack_blob(lin, lmap, p.data(), lblob);
+  for (int q = 0; q < lin.blob_total; q++) REQUIRE(blob[q] == lblob[q]);
+  REQUIRE(make_plan(d, o, pl, err, true, 2) == SIM_E_ARG && make_plan(d, o, pl, err, true, -1) == SIM_E_ARG);
+  REQUIRE(make_plan(d, o, pl, err, false, 2) == SIM_OK && !pl.bil);  // (u_z is the bilinear plan's alone)
+}
+
 int main() {
   using namespace ktrain;
+  for (int u_z = 0; u_z < 2; u_z++) {
+    check_bilinear({8, 64, 64, 64, 64, 24}, 5, 5, u_z);  // the reference's shape
+    check_bilinear({8, 64, 64, 40}, 5, 1, u_z);
+    check_bilinear({8, 64, 64}, 8, 5, u_z);              // four feature tiles, the most inputs
+    check_bilinear({3, 17, 5}, 1, 64, u_z);
+    check_bilinear({8, 33, 64, 1, 16}, 3, 2, u_z);
+  }
   check_shape({8, 64, 64, 64, 64, 24}, 5, 5);  // the reference's encoder
   check_shape({8, 64, 64, 40}, 5, 1);          // three last-layer tiles
   check_shape({8, 64, 64}, 5, 5);              // four
