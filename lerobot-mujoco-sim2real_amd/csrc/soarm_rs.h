@@ -319,23 +319,29 @@ DEVI void rs_solve(Sim<NA, NF>& S, const RowLds& L, const MInv<NA, NF>& Mi, cons
     // (loaded once: the sweeps' asm statements keep LICM from hoisting the model loads, which would
     // otherwise be re-issued and waited for in every sweep)
     asm volatile("" : "+s"(iters), "+s"(scale), "+s"(tol));
-    bool done = false;
     PHASE_T(rp0);  // (the RS solve's split: prof_rs_split)
-    PROF_DECL(int wsw = 0);
-    for (int it = 0; it < iters; it++) {
-      PROF_DO(wsw = it + 1);
-      if (!done) {
-        PROF_DO(nsweep = it + 1);
-        const float s0A = sA.x, s0B = sB.x;
-        sA.y = 0.f, sB.y = 0.f;
-        rs_sweep<NA, LY>(sA, sB, CA, CB, NF_, NH_);
-        // improvement = sum_r AR_rr / 2 Delta f_r (s0 + s1)_r, Delta f_r = the row's own step (y)
-        float P = hdA * sA.y * (s0A + sA.x);
-        P = fmaf(hdB * sB.y, s0B + sB.x, P);
-        done = rowsum16(P) * scale < tol;
-      }
-      if (__all(done)) break;
-    }
+    // The sweep loop.  An env's lanes leave it at the sweep whose improvement passes the stop test
+    // (they drop out of the active mask once, there), and the loop ends when no env is left or at the
+    // cap: the count is wave-uniform and stays on the scalar unit, so the back edge is the verdict's
+    // compare, the mask update and one branch.  (It was `if (!done) {...} if (__all(done)) break`: the
+    // mask re-derived from `done` every sweep, a per-lane count, two taken branches -- 712 against
+    // 647 cycles per sweep iteration in tools/mb_rs_tail.hip)
+    int it = 0;
+    PROF_DECL(int pis = 0);  // (profiling build: the env's sweeps, counted per lane beside the scalar count)
+    if (iters > 0) do {
+      const float s0A = sA.x, s0B = sB.x;
+      sA.y = 0.f, sB.y = 0.f;
+      rs_sweep<NA, LY>(sA, sB, CA, CB, NF_, NH_);
+      // improvement = sum_r AR_rr / 2 Delta f_r (s0 + s1)_r, Delta f_r = the row's own step (y)
+      float P = hdA * sA.y * (s0A + sA.x);
+      P = fmaf(hdB * sB.y, s0B + sB.x, P);
+      it++;
+      asm volatile("" : "+s"(it));
+      PROF_DO(pis++);
+      if (rowsum16(P) * scale < tol) break;  // (per env: all 16 lanes hold the same bits)
+    } while (it < iters);
+    PROF_DO(nsweep = pis);
+    PROF_DECL(const int wsw = wave_max_i(pis));  // the wave's sweeps: its slowest env's
     PHASE_T(rp1);
     // qacc = qacc_smooth + sum_q W_q f_q (NH_ = fl - f on the frictionloss rows, NF_ = -f on the
     // others): lane i < NV sums dof i, then the row broadcasts it
