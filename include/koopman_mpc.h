@@ -125,7 +125,7 @@ int sim_koopman_predict(sim_koopman* k, int n, int T, const float* rows, int ld,
 
 /* Training (train(), train.py:89-266, with k_linear_loss, models/losses.py:54-129, loss_name "mse"):
    one step of the DKUC model's fit is two launches -- the loss and its gradient, then the reduction
-   and Adam -- with no host synchronisation.
+   and Adam -- with no host synchronisation.  (loss_name "nmse" and "weighted_mse": set_loss, below.)
 
    The trainer owns, on one device: the parameter vector (float64), Adam's m and v, the step count of
    the bias correction, the MFMA-fragment copies the kernels read and a per-wave partial-gradient
@@ -176,7 +176,34 @@ int sim_koopman_predict(sim_koopman* k, int n, int T, const float* rows, int ld,
    H_c (u_c z), its adjoint dH_c += lambda_{i+1} (u_c z^_i)' and lambda_i = g_i + A' lambda_{i+1} +
    sum_c u_c H_c' lambda_{i+1}; u is data and has no gradient.  The sparsity and spectral-radius terms
    of H that k_linear_loss computes but leaves out of total_loss are not built either.
-   create_bilinear: SIM_E_ARG for u_z other than 0 or 1; every other refusal as create's. */
+   create_bilinear: SIM_E_ARG for u_z other than 0 or 1; every other refusal as create's.
+
+   The loss (k_linear_loss's loss_name, BaseLoss, models/losses.py:35-52) is a property of the trainer:
+   a new one is SIM_KLOSS_MSE, the loss above; sim_koopman_trainer_set_loss selects how later
+   loss_grad / train_step calls launch and touches nothing else (not the parameters, Adam's state or the
+   step count; no allocation: the workspace of every loss is made by create).  Both other losses apply
+   BaseLoss to the same four pairs -- koopman (z^, Psi(x)), pred, dis, angle -- per step, combined with
+   beta_i / cont as above; recon stays exactly 0 with a zero gradient.  With e = z^_{i+1} - Psi(x_{t0+i+1}),
+   ex its x columns:
+     SIM_KLOSS_NMSE  mse(preds, labels) / mean(labels^2) = sum (preds - labels)^2 / sum labels^2 over the
+       whole minibatch: koopman_i = sum e^2 / sum Psi(x)^2, pred_i = sum ex^2 / sum x^2, dis / angle the same
+       over their columns.  The label is not detached in the reference: koopman's normaliser depends on the
+       encoder and carries a gradient, which the step includes.  A zero normaliser gives inf or NaN as in
+       torch; it is not guarded.  The normalisers must precede every backward, so this step is four
+       launches (the sums, their reduction, then the two above).
+     SIM_KLOSS_WEIGHTED_MSE  (mse(first three columns) + 9 mse(the other columns)) / 10; the split at column
+       3 is the reference's literal constant, not npos, and needs x_dim >= 4.  dis and angle split their own
+       slice at its column 3: a slice of three columns or fewer has no "other columns", the reference's
+       value is then NaN (the mean of an empty tensor) and so is this one -- dis with the default npos = 3,
+       angle with x_dim - npos <= 3.  They are logged, not trained: total and the gradient stay finite.
+   The reference's fourth name, mae, is its evaluation metric (sim_koopman_predict), not a training choice
+   of args.py, and is not built.
+   set_loss: SIM_E_ARG for a NULL tr, an unknown id, or SIM_KLOSS_WEIGHTED_MSE with x_dim < 4; the trainer
+   then keeps its loss.  get_loss: the id, or SIM_E_ARG for NULL. */
+#define SIM_KLOSS_MSE 0
+#define SIM_KLOSS_NMSE 1
+#define SIM_KLOSS_WEIGHTED_MSE 2
+
 typedef struct sim_koopman_train_opts {
   int32_t struct_size; /* sizeof(sim_koopman_train_opts) */
   int32_t abi_version; /* SIM_ABI_VERSION */
@@ -197,6 +224,8 @@ int sim_koopman_trainer_nparam_bilinear(const sim_koopman_desc* desc);
 int sim_koopman_trainer_create_bilinear(const sim_koopman_desc* desc, const double* params, int u_z, int max_batch,
                                         const sim_koopman_train_opts* opts, int device, sim_koopman_trainer** out);
 void sim_koopman_trainer_free(sim_koopman_trainer* tr);
+int sim_koopman_trainer_set_loss(sim_koopman_trainer* tr, int loss);
+int sim_koopman_trainer_get_loss(const sim_koopman_trainer* tr);
 int sim_koopman_trainer_get_params(sim_koopman_trainer* tr, double* host_params);
 int sim_koopman_trainer_set_params(sim_koopman_trainer* tr, const double* host_params, int reset_optimizer);
 int sim_koopman_loss_grad(sim_koopman_trainer* tr, int n, int N, int T, const float* rows, int ld, int x_off,

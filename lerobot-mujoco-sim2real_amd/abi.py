@@ -164,7 +164,10 @@ EXPORTS = [
     "sim_koopman_trainer_get_params", "sim_koopman_trainer_set_params",
     "sim_koopman_loss_grad", "sim_koopman_train_step",
     "sim_koopman_trainer_nparam_bilinear", "sim_koopman_trainer_create_bilinear",
+    "sim_koopman_trainer_set_loss", "sim_koopman_trainer_get_loss",
 ]
+# SIM_KLOSS_* (include/koopman_mpc.h): the trainer's loss ids by the reference's loss_name
+KLOSS = {"mse": 0, "nmse": 1, "weighted_mse": 2}
 PROF_KINDS = ["step_fused", "collide", "substep", "geom"]
 
 _lib = None
@@ -224,6 +227,8 @@ def load_lib(path=None):
                                                         C.POINTER(vp)]
     lib.sim_koopman_trainer_free.argtypes = [vp]
     lib.sim_koopman_trainer_free.restype = None
+    lib.sim_koopman_trainer_set_loss.argtypes = [vp, ip]
+    lib.sim_koopman_trainer_get_loss.argtypes = [vp]
     lib.sim_koopman_trainer_get_params.argtypes = [vp, vp]
     lib.sim_koopman_trainer_set_params.argtypes = [vp, vp, ip]
     lib.sim_koopman_loss_grad.argtypes = [vp, ip, ip, ip, vp, ip, ip, ip, vp, ip, vp, vp, vp]

@@ -1,10 +1,11 @@
 """Training the DKUC and DBKN Koopman models on the device: the fused loss / gradient / Adam step.
 
 Reference: ``train()`` (``train.py:89-266``) over ``k_linear_loss`` (``models/losses.py:54-129``,
-``loss_name = "mse"``) with ``torch.optim.Adam`` and ``ExponentialLR(0.99)``.  One step there is six
-encoder calls, five ``lA`` / ``lB`` steps, about fifteen MSE reductions, their autograd backward
-and the optimizer; here it is two kernel launches (``include/koopman_mpc.h``
-``sim_koopman_train_step``, ``csrc/koopman_train.hip``) that read the rollout in place:
+``loss_name`` ``"mse"``, ``"nmse"`` or ``"weighted_mse"``: ``BaseLoss``, ``models/losses.py:35-52``) with
+``torch.optim.Adam`` and ``ExponentialLR(0.99)``.  One step there is six encoder calls, five ``lA`` / ``lB``
+steps, about fifteen loss reductions, their autograd backward and the optimizer; here it is two kernel
+launches (four for ``nmse``, whose normalisers are sums over the minibatch that every backward needs;
+``include/koopman_mpc.h`` ``sim_koopman_train_step``, ``csrc/koopman_train.hip``) that read the rollout in place:
 
 * :class:`KoopmanTrainer` -- the device trainer of one ``Koopmanlinear``: :meth:`loss_grad`,
   :meth:`step`, :meth:`get_params` / :meth:`set_params`, :meth:`to_net`;
@@ -16,9 +17,11 @@ and the optimizer; here it is two kernel launches (``include/koopman_mpc.h``
   generator, a window start drawn per step, ``lr * 0.99^epoch``, ``MPCController.evaluate`` every
   ``eval_interval`` epochs, the best parameters kept; the trainer is picked by the net's type.
 
-Built: DKUC and the bilinear DBKN (``net.H``, both ``u_z`` orders) with the ``mse`` loss.  The DKN /
-DKAC input encoders, the other loss names and the two regularisers ``k_linear_loss`` leaves out of
-``total_loss`` (DBKN's ``‖H‖₁`` among them) are refused, not ignored.  :class:`KoopmanTrainer` itself
+Built: DKUC and the bilinear DBKN (``net.H``, both ``u_z`` orders) with the reference's three training
+losses.  Under ``weighted_mse`` the logged ``dis`` (and ``angle`` when ``x_dim - npos <= 3``) is NaN, as the
+reference's is: the slice has no column past its third.  The DKN / DKAC input encoders, ``mae`` (the
+reference's evaluation metric, not among its training choices) and the two regularisers ``k_linear_loss``
+leaves out of ``total_loss`` (DBKN's ``‖H‖₁`` among them) are refused, not ignored.  :class:`KoopmanTrainer` itself
 still refuses a net with ``H``: a DBKN net trained as DKUC would silently lose its bilinear term.
 There is no CPU path.
 """
@@ -108,7 +111,7 @@ class KoopmanTrainer:
     ``net``: this project's ``Koopmanlinear``; it is read at construction and not touched again
     (:meth:`to_net` writes the trained parameters back).  ``max_batch``: the largest minibatch.
     ``pre_length``, ``npos``, ``gamma`` as the reference's args (5, 3, 0.8); ``betas``, ``eps``
-    Adam's.  ``loss_name`` must be ``"mse"``."""
+    Adam's.  ``loss_name``: ``"mse"``, ``"nmse"`` or ``"weighted_mse"`` (``x_dim >= 4``)."""
 
     _check = staticmethod(_check_net)
 
@@ -123,8 +126,9 @@ class KoopmanTrainer:
                  loss_name="mse"):
         import torch
 
-        if loss_name != "mse":
-            raise NotImplementedError(f"{type(self).__name__}: loss_name {loss_name!r} is not built; 'mse' only")
+        if loss_name not in abi.KLOSS:
+            raise NotImplementedError(f"{type(self).__name__}: loss_name {loss_name!r} is not built; "
+                                      "'mse', 'nmse', 'weighted_mse' only")
         self._h = None
         self._check(net)
         if not torch.cuda.is_available():
@@ -151,6 +155,16 @@ class KoopmanTrainer:
         self.nparam, self.max_batch = n, int(max_batch)
         self._h = C.c_void_p()
         abi.check(self.lib, self._create(d, p, max_batch, o, device))
+        rc = self.lib.sim_koopman_trainer_set_loss(self._h, abi.KLOSS[loss_name])
+        if rc == abi.E_ARG:
+            raise ValueError(f"{type(self).__name__}: {self.lib.sim_last_error().decode()}")
+        abi.check(self.lib, rc)
+
+    @property
+    def loss_name(self):
+        """The trainer's loss, by the reference's name."""
+        k = self.lib.sim_koopman_trainer_get_loss(self._h)
+        return next(name for name, v in abi.KLOSS.items() if v == k)
 
     def __del__(self):
         try:
@@ -253,7 +267,7 @@ def schedule(seed, n_traj, steps, pre_length, batch_size, epochs):
 
 
 def train(net, rollout, args=None, epochs=10, batch_size=128, lr=1e-3, lr_decay=0.99, seed=0, eval_rollout=None,
-          eval_interval=1, device=0, pre_length=5, gamma=0.8, npos=3):
+          eval_interval=1, device=0, pre_length=5, gamma=0.8, npos=3, loss_name="mse"):
     """The reference's training loop on a device rollout [T+1, N, u_dim + x_dim] (``rollout_device``).
 
     Adam at ``lr`` decayed by ``lr_decay`` per epoch (``ExponentialLR``), the minibatches and window
@@ -262,7 +276,7 @@ def train(net, rollout, args=None, epochs=10, batch_size=128, lr=1e-3, lr_decay=
     ``MPCController.evaluate`` on ``eval_rollout`` (default: ``rollout``); the parameters with the
     lowest ``avg_error`` are kept and are in ``net`` on return.  ``args``: the controller's args
     (x_dim, u_dim, MPC_type); default from the net.  Returns the history dict: ``train_loss`` [epochs][6]
-    (the mean of the epoch's step losses), ``lr``, ``eval`` [(epoch, avg, dis, angle)], ``best_epoch``,
+    (the mean of the epoch's step losses under ``loss_name``; its dis column is NaN for ``weighted_mse`` at npos <= 3), ``lr``, ``eval`` [(epoch, avg, dis, angle)], ``best_epoch``,
     ``best_error``, ``best_params``."""
     import torch
 
@@ -276,7 +290,7 @@ def train(net, rollout, args=None, epochs=10, batch_size=128, lr=1e-3, lr_decay=
     ev = r if eval_rollout is None else torch.as_tensor(eval_rollout).to(device=dev, dtype=torch.float32).contiguous()
     T, N = r.shape[0] - 1, r.shape[1]
     cls = BilinearKoopmanTrainer if _has_h(net) else KoopmanTrainer  # DBKN / DKUC
-    tr = cls(net, min(batch_size, N), device=device, pre_length=pre_length, npos=npos, gamma=gamma)
+    tr = cls(net, min(batch_size, N), device=device, pre_length=pre_length, npos=npos, gamma=gamma, loss_name=loss_name)
     sched = schedule(seed, N, T, pre_length, batch_size, epochs)
     hist = dict(train_loss=[], lr=[], eval=[], best_epoch=-1, best_error=float("inf"), best_params=tr.get_params())
     for ep, batches in enumerate(sched):

@@ -30,6 +30,12 @@
 //     index map.  The bias correction's step count lives on the device: k_koopman_grad's first
 //     thread advances it (stream order makes it visible to k_koopman_apply), so steps queue
 //     without a host round trip.
+// The loss (BaseLoss: mse, nmse, weighted_mse; sim_koopman_trainer_set_loss) is a template parameter of both:
+// weighted_mse is the same two launches with other constants.  nmse divides by sums over the whole
+// minibatch that every sample's backward needs, so two launches precede them:
+//   k_koopman_stats       the forward alone, per wave and step the sums of squared errors and labels;
+//   k_koopman_nmse_table  one workgroup adds them in a fixed order into the per-step coefficients and the losses.
+// No grid-wide barrier, no wave waits on another: stream order is the only dependency.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -226,6 +232,72 @@ DEVI void encode_backward(const KDev& K, const TDev& D, const double* blob, doub
   layer_backward<KT, 1, false>(tile, slot + D.sw[0], slot + D.sb[0], blob, lane, ain, dl, first);
 }
 
+// z^_{i+1} = [A | B] [z^_i; u_i] (+ the bilinear term) for the wave's 16 samples, from z^_i = (zx, zf)
+// and u_i = ub in the B layout: zn's tile 0 = the x rows, tiles 1.. = the features.  AB: [A | B]'s
+// fragments + lane (opaque).  k_koopman_stats' rollout; k_koopman_grad carries the same lines in its
+// loop (called from there the compiler allocates that kernel's registers differently, and it has none
+// to spare)
+template <int NTL, bool BIL>
+DEVI void model_step(const KDev& K, const TDev& D, const double* blob, const double* AB, int lane,
+                     const double (&zx)[2], const d4 (&zf)[KT], const double (&ub)[2], d4 (&zn)[1 + NTL]) {
+  constexpr int NZT = 1 + NTL;            // tiles of the lifted state
+  constexpr int ABKS = 2 + 4 * NTL + 2;   // k-steps of [A | B]
+  constexpr int ATKS = 2 + 4 * NTL;       // k-steps of A'
+  const int col = lane & 15;
+#pragma unroll
+  for (int q = 0; q < NZT; q++) zn[q] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int s0 = 0; s0 < ABKS; s0 += 4) {  // (ABKS is a multiple of 4) 4 NZT fragment loads, then their MFMAs
+    double w[4][NZT];
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+      for (int q = 0; q < NZT; q++) w[j][q] = AB[(q * ABKS + s0 + j) * 64];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int s = s0 + j;
+      const double b = s < 2 ? zx[s] : (s < 2 + 4 * NTL ? zf[(s - 2) >> 2][(s - 2) & 3] : ub[s - 2 - 4 * NTL]);
+#pragma unroll
+      for (int q = 0; q < NZT; q++) zn[q] = mfma(w[j][q], b, zn[q]);
+    }
+    sched_fence();
+  }
+  if constexpr (BIL) {  // + sum_c H_c (u_c z^_i): A's k-loop per c, the B operand scaled by the sample's u_c
+    for (int c = 0; c < K.ud; c++) {
+      // ub is in the B layout: u_c sits in register c >> 2 of the lane with kq = c & 3 and this column
+      const double uc = __shfl(c < 4 ? ub[0] : ub[1], (c & 3) * 16 + col);
+      const double* HF = opaque(blob + D.at + (size_t)(1 + c) * (NZT * ATKS * 64) + lane);
+      double sz[ATKS];
+      sz[0] = uc * zx[0], sz[1] = uc * zx[1];
+#pragma unroll
+      for (int q = 0; q < NTL; q++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) sz[2 + 4 * q + r] = uc * zf[q][r];
+#pragma unroll
+      for (int s0 = 0; s0 < ATKS; s0 += 2) {  // (ATKS is even) 2 NZT fragment loads, then their MFMAs
+        double w[2][NZT];
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+          for (int q = 0; q < NZT; q++) w[j][q] = HF[(q * ATKS + s0 + j) * 64];
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+          for (int q = 0; q < NZT; q++) zn[q] = mfma(w[j][q], sz[s0 + j], zn[q]);
+        sched_fence();
+      }
+    }
+  }
+}
+
+// the per-step table of the nmse loss (k_koopman_nmse_table): read from a wave-uniform address in the
+// constant address space, so it costs scalar loads and no VGPRs
+typedef const double __attribute__((address_space(4))) * ctab_t;
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+DEVI ctab_t tab_of(const int* step) { return (ctab_t)(reinterpret_cast<const double*>(step) + ktrain::STEP_DOUBLES); }
+#pragma clang diagnostic pop
+
 // (blob, ws and scratch are not __restrict__: the fragment loads of [A | B], A' and the last layer's W'
 // are invariant across the steps, and with the promise that the slot's stores do not alias them the
 // compiler keeps all of them in registers across the loop -- 200 VGPRs at four feature tiles, and spills)
@@ -235,7 +307,18 @@ DEVI void encode_backward(const KDev& K, const TDev& D, const double* blob, doub
 // then the H_c' ones; dH_c's tiles [ud][NZT][NZT] right after [dA | dB] in the slot.  u_c of the lane's
 // sample is a scalar on the N side, so it scales the B operand (forward), the transposed z^ tiles
 // (dH_c = lambda_{i+1} (u_c z^_i)') and the C/D output (u_c H_c' lambda_{i+1}); c is a runtime loop.
-template <int NTL, bool BIL>
+//
+// LOSS (include/koopman_mpc.h SIM_KLOSS_*) changes g_{i+1}, the target encode's output gradient and the
+// loss partials alone; the kernel sits at the register limit, so the choice is made at compile time.
+//   mse           g = c_i (2 / (n nz) e, + 2 / (n x_dim) ex on the x rows); four sums (koopman, pred, dis, angle).
+//   weighted_mse  g = c_i 2 weight(row) e: per-lane constants for the x tile's two registers, one scalar for
+//                 the features.  The "first three columns" / "rest" halves of the four sums: per lane the
+//                 x tile's two rows and the features are summed apart and sorted into the halves at the end.
+//   nmse          g = c_i (2 / D^k_i e, + 2 / D^p_i ex on the x rows); the label is not detached, so the
+//                 target encode's output gradient gains -c_i 2 N^k_i / (D^k_i)^2 z_f.  The coefficients come
+//                 from the table [P][4] (k_koopman_nmse_table) that follows the step count in step's buffer
+//                 (tab_of: the argument list is the same for every loss), the losses too: no sums here.
+template <int NTL, bool BIL, int LOSS>
 __global__ __launch_bounds__(256) void k_koopman_grad(KDev K, TDev D, const double* blob, int n, int N,
                                                        const float* __restrict__ rows, int ld, int x_off, int u_off,
                                                        const int* __restrict__ traj_idx, int t0,
@@ -266,13 +349,24 @@ __global__ __launch_bounds__(256) void k_koopman_grad(KDev K, TDev D, const doub
     double b = 1.0;
     for (int i = 0; i < P; i++) cont += b, b *= D.gamma;
   }
-  const double ck = 2.0 / ((double)n * K.nz), cp = 2.0 / ((double)n * K.xd);
+  // mse: the two means' factors.  weighted_mse: wx[s] = 2 (koopman's + pred's weight) of x row 4 s + kq
+  // (rows >= x_dim carry a zero error), ck = 2 the feature rows' one weight
+  double ck = 2.0 / ((double)n * K.nz), cp = 2.0 / ((double)n * K.xd);
+  double wx[2] = {0.0, 0.0};
+  if constexpr (LOSS == SIM_KLOSS_WEIGHTED_MSE) {
+    const double lo = 2.0 / (30.0 * n), hk = 18.0 / (10.0 * n * (K.nz - 3)), hp = 18.0 / (10.0 * n * (K.xd - 3));
+#pragma unroll
+    for (int s = 0; s < 2; s++) wx[s] = 4 * s + kq < 3 ? lo + lo : hk + hp;
+    ck = hk;
+  }
+  ctab_t ct = tab_of(step);
 
   double x0[2], zx[2];
   load_pair(r0 + x_off, live, K.xd, kq, x0);
   d4 zf[KT];
   encode<NTL>(K, lds, lane, x0, zf);
   zx[0] = x0[0], zx[1] = x0[1];
+  // mse: koopman, pred, dis, angle.  weighted_mse: x row kq, x row 4 + kq, the features (sd)
   double sk = 0.0, sp = 0.0, sd = 0.0, sa = 0.0;
   double gx[2] = {0.0, 0.0};
   d4 gf[NTL];
@@ -342,21 +436,30 @@ __global__ __launch_bounds__(256) void k_koopman_grad(KDev K, TDev D, const doub
     // the error, the loss partials, g_{i+1}
     const double c = beta / cont;
     d4 dl[KT];
+    if constexpr (LOSS == SIM_KLOSS_NMSE) ck = 2.0 * ct[4 * i], cp = 2.0 * ct[4 * i + 2];  // 2 / D^k_i, 2 / D^p_i
 #pragma unroll
     for (int s = 0; s < 2; s++) {
       const int row = 4 * s + kq;
       const double ex = live ? zn[0][s] - xn[s] : 0.0;  // (rows >= x_dim: both are zero)
       const double e2 = beta * ex * ex;
-      sk += e2, sp += e2;
-      if (row < D.npos) sd += e2; else sa += e2;
-      gx[s] = c * (ck + cp) * ex;
+      if constexpr (LOSS == SIM_KLOSS_MSE) {
+        sk += e2, sp += e2;
+        if (row < D.npos) sd += e2; else sa += e2;
+      }
+      if constexpr (LOSS == SIM_KLOSS_WEIGHTED_MSE) {
+        if (s == 0) sk += e2; else sp += e2;
+        gx[s] = c * wx[s] * ex;
+      } else {
+        gx[s] = c * (ck + cp) * ex;
+      }
     }
 #pragma unroll
     for (int q = 0; q < NTL; q++)
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         const double ef = live ? zn[1 + q][r] - out[q][r] : 0.0;  // (rows >= the output width: both zero)
-        sk += beta * ef * ef;
+        if constexpr (LOSS == SIM_KLOSS_MSE) sk += beta * ef * ef;
+        if constexpr (LOSS == SIM_KLOSS_WEIGHTED_MSE) sd += beta * ef * ef;
         gf[q][r] = c * ck * ef;
       }
     double* sg = si + NZT * 256;  // g_{i+1}: [i][1][tile][r][64]
@@ -370,6 +473,11 @@ __global__ __launch_bounds__(256) void k_koopman_grad(KDev K, TDev D, const doub
     for (int T = 0; T < KT; T++) dl[T] = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int q = 0; q < NTL; q++) dl[q] = -gf[q];
+    if constexpr (LOSS == SIM_KLOSS_NMSE) {  // the normaliser D^k_i's own gradient: -c_i 2 N^k_i / (D^k_i)^2 z_f
+      const double cn = live ? c * 2.0 * ct[4 * i + 1] : 0.0;
+#pragma unroll
+      for (int q = 0; q < NTL; q++) dl[q] -= cn * out[q];
+    }
     encode_backward<NTL>(K, D, blob, tile, slot, lane, xn, hs, dl, i == 0);
     zx[0] = zn[0][0], zx[1] = zn[0][1];
 #pragma unroll
@@ -510,14 +618,142 @@ __global__ __launch_bounds__(256) void k_koopman_grad(KDev K, TDev D, const doub
     encode_backward<NTL>(K, D, blob, tile, slot, lane, x0, hs, dl, false);
   }
   // the wave's loss sums: a fixed butterfly, the same bits in every lane
+  if constexpr (LOSS == SIM_KLOSS_MSE) {
 #pragma unroll
-  for (int m = 1; m < 64; m <<= 1) {
-    sk += __shfl_xor(sk, m), sp += __shfl_xor(sp, m);
-    sd += __shfl_xor(sd, m), sa += __shfl_xor(sa, m);
+    for (int m = 1; m < 64; m <<= 1) {
+      sk += __shfl_xor(sk, m), sp += __shfl_xor(sp, m);
+      sd += __shfl_xor(sd, m), sa += __shfl_xor(sa, m);
+    }
+    if (lane == 0) {
+      double* sl = slot + D.slot_stride - 8;
+      sl[0] = sk, sl[1] = sp, sl[2] = sd, sl[3] = sa;
+    }
   }
-  if (lane == 0) {
-    double* sl = slot + D.slot_stride - 8;
-    sl[0] = sk, sl[1] = sp, sl[2] = sd, sl[3] = sa;
+  if constexpr (LOSS == SIM_KLOSS_WEIGHTED_MSE) {
+    // the lane's two x rows into the halves: [0] columns < 3 of x, [1] the other x columns, [2] the
+    // features, then dis (columns < npos) and angle (the rest) split at their own column 3
+    double v[7] = {0.0, 0.0, sd, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+      const int row = 4 * s + kq;
+      const bool dis = row < D.npos, own = (dis ? row : row - D.npos) < 3;  // (selects: v stays in registers)
+      const double e2 = s == 0 ? sk : sp;
+      v[0] += row < 3 ? e2 : 0.0, v[1] += row < 3 ? 0.0 : e2;
+      v[3] += dis && own ? e2 : 0.0, v[4] += dis && !own ? e2 : 0.0;
+      v[5] += !dis && own ? e2 : 0.0, v[6] += !dis && !own ? e2 : 0.0;
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1)
+#pragma unroll
+      for (int k = 0; k < 7; k++) v[k] += __shfl_xor(v[k], m);
+    if (lane == 0) {  // koopman, pred, dis, angle: each its first three columns, then its rest
+      double* sl = slot + D.slot_stride - 8;
+      sl[0] = v[0], sl[1] = v[1] + v[2], sl[2] = v[0], sl[3] = v[1];
+      sl[4] = v[3], sl[5] = v[4], sl[6] = v[5], sl[7] = v[6];
+    }
+  }
+}
+
+// the nmse normalisers, forward only: k_koopman_grad's mapping, early return and rollout of z^ with the
+// plain encode of each target; per wave and step the partial sums
+//   stat[wave][i][8] = N^k, D^k, N^p, D^p, N^dis, D^dis, N^ang, D^ang
+// (N: squared errors, D: squared labels; k over all of z, p over x, dis / ang over x's columns < / >= npos),
+// a fixed butterfly and one lane's stores.  Every wave below ceil(n / 16) writes all P rows.
+template <int NTL, bool BIL>
+__global__ __launch_bounds__(256) void k_koopman_stats(KDev K, TDev D, const double* blob, int n, int N,
+                                                        const float* __restrict__ rows, int ld, int x_off, int u_off,
+                                                        const int* __restrict__ traj_idx, int t0, double* stat) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  stage(lds, blob, K.total);
+  constexpr int NZT = 1 + NTL;
+  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, kq = lane >> 4, col = lane & 15;
+  const int wave = blockIdx.x * (blockDim.x >> 6) + wid;
+  if (wave * 16 >= n) return;  // (whole waves: no workgroup barrier below)
+  const int e = wave * 16 + col;
+  const bool live = e < n;
+  int tr = 0;
+  if (live) tr = traj_idx ? min(max(traj_idx[e], 0), N - 1) : e;
+  const size_t ts = (size_t)N * ld;
+  const float* __restrict__ r0 = rows + (size_t)t0 * ts + (size_t)tr * ld;
+  double* st = stat + (size_t)wave * D.P * 8;
+  double zx[2];
+  load_pair(r0 + x_off, live, K.xd, kq, zx);
+  d4 zf[KT];
+  encode<NTL>(K, lds, lane, zx, zf);
+  for (int i = 0; i < D.P; i++) {
+    const float* __restrict__ ri = r0 + (size_t)i * ts;
+    double ub[2], xn[2];
+    load_pair(ri + u_off, live, K.ud, kq, ub);
+    load_pair(ri + ts + x_off, live, K.xd, kq, xn);
+    d4 zn[NZT], out[KT];
+    model_step<NTL, BIL>(K, D, blob, opaque(blob + D.ab + lane), lane, zx, zf, ub, zn);
+    encode<NTL>(K, lds, lane, xn, out);
+    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // N, D of: the features, dis, angle
+#pragma unroll
+    for (int q = 0; q < NTL; q++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const double zt = live ? out[q][r] : 0.0, ef = live ? zn[1 + q][r] - zt : 0.0;
+        v[0] += ef * ef, v[1] += zt * zt;
+      }
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+      const double ex = live ? zn[0][s] - xn[s] : 0.0;  // (xn is zero in a dead lane and in rows >= x_dim)
+      const bool dis = 4 * s + kq < D.npos;  // (selects: v stays in registers)
+      const double e2 = ex * ex, x2 = xn[s] * xn[s];
+      v[2] += dis ? e2 : 0.0, v[3] += dis ? x2 : 0.0;
+      v[4] += dis ? 0.0 : e2, v[5] += dis ? 0.0 : x2;
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1)
+#pragma unroll
+      for (int k = 0; k < 6; k++) v[k] += __shfl_xor(v[k], m);
+    if (lane == 0) {
+      const double np = v[2] + v[4], dp = v[3] + v[5];
+      double* o = st + i * 8;
+      o[0] = np + v[0], o[1] = dp + v[1], o[2] = np, o[3] = dp;
+      o[4] = v[2], o[5] = v[3], o[6] = v[4], o[7] = v[5];
+    }
+    zx[0] = zn[0][0], zx[1] = zn[0][1];
+#pragma unroll
+    for (int q = 0; q < NTL; q++) zf[q] = zn[1 + q];
+  }
+}
+
+// the nmse table, one workgroup: the waves' partials of each (step, sum) added in a fixed order (lane l
+// takes waves l, l + 64, .. in turn, then a fixed butterfly), once; then per step
+//   tab[i][4] = 1 / D^k_i, N^k_i / (D^k_i)^2, 1 / D^p_i, 0      (k_koopman_grad reads these)
+// and the six losses at tab[4 P ..].  A zero normaliser gives inf / NaN, as in torch.
+__global__ __launch_bounds__(1024) void k_koopman_nmse_table(const double* __restrict__ stat, double* __restrict__ tab,
+                                                              int nslot, int P, double gamma) {
+  __shared__ double red[ktrain::MAXP * 8];
+  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+  for (int pr = wid; pr < P * 8; pr += nw) {
+    double s = 0.0;
+    for (int w = lane; w < nslot; w += 64) s += stat[(size_t)w * P * 8 + pr];
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m);
+    if (lane == 0) red[pr] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < P) {
+    const double* r = red + 8 * threadIdx.x;
+    double* t = tab + 4 * threadIdx.x;
+    t[0] = 1.0 / r[1], t[1] = r[0] / (r[1] * r[1]), t[2] = 1.0 / r[3], t[3] = 0.0;
+  }
+  if (threadIdx.x == 0) {
+    double cont = 0.0, b = 1.0, s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = 0; i < P; i++) {
+      const double* r = red + 8 * i;
+#pragma unroll
+      for (int k = 0; k < 4; k++) s[k] += b * (r[2 * k] / r[2 * k + 1]);
+      cont += b, b *= gamma;
+    }
+    double* l = tab + 4 * P;
+    const double koop = s[0] / cont, pred = s[1] / cont;
+    l[0] = koop + pred, l[1] = koop, l[2] = pred;
+    l[3] = 0.0;  // recon: lC Psi(x) = x exactly
+    l[4] = s[2] / cont, l[5] = s[3] / cont;
   }
 }
 
@@ -531,6 +767,9 @@ struct ADev {
   const int* gidx;  // [nparam]: where a wave's slot holds the parameter's gradient
 };
 
+// LOSS: how the six losses come out of the slots' eight trailing sums (mse: four; weighted_mse: the halves
+// of each, NaN for a mean over no column, as torch's) or, for nmse, out of the table
+template <int LOSS>
 __global__ __launch_bounds__(256) void k_koopman_apply(ADev a) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p < a.nparam) {
@@ -551,36 +790,75 @@ __global__ __launch_bounds__(256) void k_koopman_apply(ADev a) {
       if (c1 >= 0) a.blob[c1] = q;
     }
   }
-  if (p == 0 && a.losses) {
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int w = 0; w < a.nslot; w++) {
-      const double* sl = a.ws + (size_t)(w + 1) * a.slot_stride - 8;
+  if constexpr (LOSS == SIM_KLOSS_MSE) {
+    if (p == 0 && a.losses) {
+      double s[4] = {0.0, 0.0, 0.0, 0.0};
+      for (int w = 0; w < a.nslot; w++) {
+        const double* sl = a.ws + (size_t)(w + 1) * a.slot_stride - 8;
 #pragma unroll
-      for (int k = 0; k < 4; k++) s[k] += sl[k];
+        for (int k = 0; k < 4; k++) s[k] += sl[k];
+      }
+      double cont = 0.0, b = 1.0;
+      for (int i = 0; i < a.P; i++) cont += b, b *= a.gamma;
+      const double nn = (double)a.n * cont;
+      const double koop = s[0] / (nn * a.nz), pred = s[1] / (nn * a.xd);
+      a.losses[0] = koop + pred;
+      a.losses[1] = koop;
+      a.losses[2] = pred;
+      a.losses[3] = 0.0;  // recon: lC Psi(x) = x exactly
+      a.losses[4] = s[2] / (nn * a.npos);
+      a.losses[5] = s[3] / (nn * (a.xd - a.npos));
     }
-    double cont = 0.0, b = 1.0;
-    for (int i = 0; i < a.P; i++) cont += b, b *= a.gamma;
-    const double nn = (double)a.n * cont;
-    const double koop = s[0] / (nn * a.nz), pred = s[1] / (nn * a.xd);
-    a.losses[0] = koop + pred;
-    a.losses[1] = koop;
-    a.losses[2] = pred;
-    a.losses[3] = 0.0;  // recon: lC Psi(x) = x exactly
-    a.losses[4] = s[2] / (nn * a.npos);
-    a.losses[5] = s[3] / (nn * (a.xd - a.npos));
+  }
+  if constexpr (LOSS == SIM_KLOSS_WEIGHTED_MSE) {
+    if (p == 0 && a.losses) {
+      double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      for (int w = 0; w < a.nslot; w++) {
+        const double* sl = a.ws + (size_t)(w + 1) * a.slot_stride - 8;
+#pragma unroll
+        for (int k = 0; k < 8; k++) s[k] += sl[k];
+      }
+      double cont = 0.0, b = 1.0;
+      for (int i = 0; i < a.P; i++) cont += b, b *= a.gamma;
+      const double nn = (double)a.n * cont;
+      // (mse of the first three columns + 9 mse of the d - 3 others) / 10 of a d-column slice
+      auto wm = [&](double lo, double hi, int d) { return d > 3 ? (lo / (nn * 3) + 9.0 * (hi / (nn * (d - 3)))) / 10.0 : NAN; };
+      const double koop = wm(s[0], s[1], a.nz), pred = wm(s[2], s[3], a.xd);
+      a.losses[0] = koop + pred;
+      a.losses[1] = koop;
+      a.losses[2] = pred;
+      a.losses[3] = 0.0;
+      a.losses[4] = wm(s[4], s[5], a.npos);
+      a.losses[5] = wm(s[6], s[7], a.xd - a.npos);
+    }
+  }
+  if constexpr (LOSS == SIM_KLOSS_NMSE) {
+    if (p < 6 && a.losses) a.losses[p] = tab_of(a.step)[4 * a.P + p];
   }
 }
 
 typedef void (*GradFn)(KDev, TDev, const double*, int, int, const float*, int, int, int, const int*, int, double*,
                        double*, int*, int);
-const GradFn GRAD[2][4] = {
-    {k_koopman_grad<1, false>, k_koopman_grad<2, false>, k_koopman_grad<3, false>, k_koopman_grad<4, false>},
-    {k_koopman_grad<1, true>, k_koopman_grad<2, true>, k_koopman_grad<3, true>, k_koopman_grad<4, true>}};
+#define GRAD_ROW(BIL, LOSS) \
+  {k_koopman_grad<1, BIL, LOSS>, k_koopman_grad<2, BIL, LOSS>, k_koopman_grad<3, BIL, LOSS>, k_koopman_grad<4, BIL, LOSS>}
+const GradFn GRAD[3][2][4] = {{GRAD_ROW(false, SIM_KLOSS_MSE), GRAD_ROW(true, SIM_KLOSS_MSE)},  // [loss][bil][ntl - 1]
+                              {GRAD_ROW(false, SIM_KLOSS_NMSE), GRAD_ROW(true, SIM_KLOSS_NMSE)},
+                              {GRAD_ROW(false, SIM_KLOSS_WEIGHTED_MSE), GRAD_ROW(true, SIM_KLOSS_WEIGHTED_MSE)}};
+#undef GRAD_ROW
+typedef void (*ApplyFn)(ADev);
+const ApplyFn APPLY[3] = {k_koopman_apply<SIM_KLOSS_MSE>, k_koopman_apply<SIM_KLOSS_NMSE>, k_koopman_apply<SIM_KLOSS_WEIGHTED_MSE>};
+
+typedef void (*StatsFn)(KDev, TDev, const double*, int, int, const float*, int, int, int, const int*, int, double*);
+const StatsFn STATS[2][4] = {
+    {k_koopman_stats<1, false>, k_koopman_stats<2, false>, k_koopman_stats<3, false>, k_koopman_stats<4, false>},
+    {k_koopman_stats<1, true>, k_koopman_stats<2, true>, k_koopman_stats<3, true>, k_koopman_stats<4, true>}};
 
 }  // namespace
 
 struct sim_koopman_trainer {
   int device = 0, max_batch = 0, max_slot = 0;
+  int loss = SIM_KLOSS_MSE;  // how loss_grad / train_step launch (sim_koopman_trainer_set_loss)
+  double* d_stat = nullptr;  // nmse: the waves' sums [max_slot][P][8]; its table follows the count in d_step
   sim_koopman_train_opts opts{};
   ktrain::Plan pl{};
   KDev kd{};
@@ -623,9 +901,17 @@ int launch(sim_koopman_trainer* t, int n, int N, int T, const float* rows, int l
   if (n == 0) return SIM_OK;
   const ktrain::Plan& pl = t->pl;
   const int waves = (n + 15) / 16;
-  hipLaunchKernelGGL(GRAD[pl.bil][pl.ntl - 1], dim3((waves + ktrain::WAVES - 1) / ktrain::WAVES), dim3(64 * ktrain::WAVES),
-                     pl.lds_bytes, (hipStream_t)stream, t->kd, t->td, t->d_blob, n, N, rows, ld, x_off, u_off,
-                     (const int*)traj_idx, t0, t->d_ws, t->d_scr, t->d_step, update);
+  const dim3 grid((waves + ktrain::WAVES - 1) / ktrain::WAVES), block(64 * ktrain::WAVES);
+  if (t->loss == SIM_KLOSS_NMSE) {  // the normalisers first: every sample's backward needs the whole batch's
+    hipLaunchKernelGGL(STATS[pl.bil][pl.ntl - 1], grid, block, pl.lds_bytes, (hipStream_t)stream, t->kd, t->td, t->d_blob,
+                       n, N, rows, ld, x_off, u_off, (const int*)traj_idx, t0, t->d_stat);
+    TCHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_koopman_nmse_table, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const double*)t->d_stat,
+                       reinterpret_cast<double*>(t->d_step) + ktrain::STEP_DOUBLES, waves, pl.P, t->opts.gamma);
+    TCHECK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(GRAD[t->loss][pl.bil][pl.ntl - 1], grid, block, pl.lds_bytes, (hipStream_t)stream, t->kd, t->td,
+                     t->d_blob, n, N, rows, ld, x_off, u_off, (const int*)traj_idx, t0, t->d_ws, t->d_scr, t->d_step, update);
   TCHECK(hipGetLastError());
   ADev a{};
   a.nparam = pl.nparam, a.nslot = waves, a.slot_stride = pl.slot_stride, a.n = n, a.P = pl.P, a.xd = pl.xd;
@@ -633,7 +919,7 @@ int launch(sim_koopman_trainer* t, int n, int N, int T, const float* rows, int l
   a.gamma = t->opts.gamma, a.lr = lr, a.beta1 = t->opts.beta1, a.beta2 = t->opts.beta2, a.eps = t->opts.eps;
   a.ws = t->d_ws, a.grad = grad, a.losses = losses, a.params = t->d_params, a.m = t->d_m, a.v = t->d_v;
   a.blob = t->d_blob, a.step = t->d_step, a.map = t->d_map, a.gidx = t->d_gidx;
-  hipLaunchKernelGGL(k_koopman_apply, dim3((pl.nparam + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(APPLY[t->loss], dim3((pl.nparam + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
   TCHECK(hipGetLastError());
   return SIM_OK;
 }
@@ -681,12 +967,13 @@ int create(const sim_koopman_desc* desc, const double* params, bool bil, int u_z
   D.slot_stride = pl.slot_stride, D.scr_stride = pl.scr_stride, D.P = pl.P, D.npos = pl.npos, D.gamma = opts->gamma;
   const size_t np = (size_t)pl.nparam * sizeof(double);
   if (hipMalloc(&t->d_params, np) != hipSuccess || hipMalloc(&t->d_m, np) != hipSuccess ||
-      hipMalloc(&t->d_v, np) != hipSuccess || hipMalloc(&t->d_step, sizeof(int)) != hipSuccess ||
+      hipMalloc(&t->d_v, np) != hipSuccess || hipMalloc(&t->d_step, ktrain::step_bytes(pl)) != hipSuccess ||
       hipMalloc(&t->d_blob, (size_t)pl.blob_total * sizeof(double)) != hipSuccess ||
       hipMalloc(&t->d_map, t->map.size() * sizeof(int32_t)) != hipSuccess ||
       hipMalloc(&t->d_gidx, gidx.size() * sizeof(int32_t)) != hipSuccess ||
       hipMalloc(&t->d_ws, (size_t)t->max_slot * pl.slot_stride * sizeof(double)) != hipSuccess ||
-      hipMalloc(&t->d_scr, (size_t)t->max_slot * pl.scr_stride * sizeof(double)) != hipSuccess) {
+      hipMalloc(&t->d_scr, (size_t)t->max_slot * pl.scr_stride * sizeof(double)) != hipSuccess ||
+      hipMalloc(&t->d_stat, ktrain::stat_doubles(pl, t->max_slot) * sizeof(double)) != hipSuccess) {
     sim_koopman_trainer_free(t);
     return soarm_set_error(SIM_E_HIP, "hipMalloc failed");
   }
@@ -696,9 +983,12 @@ int create(const sim_koopman_desc* desc, const double* params, bool bil, int u_z
     rc = soarm_set_error(SIM_E_HIP, "hipMemcpy failed");
   if (!rc && hipMemcpy(t->d_gidx, gidx.data(), gidx.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
     rc = soarm_set_error(SIM_E_HIP, "hipMemcpy failed");
-  if (!rc && hipFuncSetAttribute((const void*)GRAD[pl.bil][pl.ntl - 1], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)ktrain::LDS_BYTES) != hipSuccess)
-    rc = soarm_set_error(SIM_E_HIP, "hipFuncSetAttribute failed");
+  // every kernel set_loss can select: the dynamic LDS is raised here, not at the first step
+  const void* dyn[4] = {(const void*)GRAD[0][pl.bil][pl.ntl - 1], (const void*)GRAD[1][pl.bil][pl.ntl - 1],
+                        (const void*)GRAD[2][pl.bil][pl.ntl - 1], (const void*)STATS[pl.bil][pl.ntl - 1]};
+  for (const void* f : dyn)
+    if (!rc && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ktrain::LDS_BYTES) != hipSuccess)
+      rc = soarm_set_error(SIM_E_HIP, "hipFuncSetAttribute failed");
   if (rc) {
     sim_koopman_trainer_free(t);
     return rc;
@@ -729,7 +1019,23 @@ void sim_koopman_trainer_free(sim_koopman_trainer* t) {
   (void)hipSetDevice(t->device);
   (void)hipFree(t->d_params), (void)hipFree(t->d_m), (void)hipFree(t->d_v), (void)hipFree(t->d_step);
   (void)hipFree(t->d_blob), (void)hipFree(t->d_map), (void)hipFree(t->d_gidx), (void)hipFree(t->d_ws), (void)hipFree(t->d_scr);
+  (void)hipFree(t->d_stat);
   delete t;
+}
+
+int sim_koopman_trainer_set_loss(sim_koopman_trainer* t, int loss) {
+  if (!t) return soarm_set_error(SIM_E_ARG, "null trainer");
+  if (loss != SIM_KLOSS_MSE && loss != SIM_KLOSS_NMSE && loss != SIM_KLOSS_WEIGHTED_MSE)
+    return soarm_set_error(SIM_E_ARG, "set_loss: unknown loss id " + std::to_string(loss));
+  if (loss == SIM_KLOSS_WEIGHTED_MSE && t->pl.xd < 4)
+    return soarm_set_error(SIM_E_ARG, "set_loss: weighted_mse splits x at column 3 and needs x_dim >= 4");
+  t->loss = loss;
+  return SIM_OK;
+}
+
+int sim_koopman_trainer_get_loss(const sim_koopman_trainer* t) {
+  if (!t) return soarm_set_error(SIM_E_ARG, "null trainer");
+  return t->loss;
 }
 
 int sim_koopman_trainer_get_params(sim_koopman_trainer* t, double* host_params) {

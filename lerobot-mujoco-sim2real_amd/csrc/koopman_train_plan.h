@@ -138,6 +138,16 @@ inline int make_plan(const sim_koopman_desc& d, const sim_koopman_train_opts& o,
   return SIM_OK;
 }
 
+// the nmse loss's workspace: the waves' per-step sums [max_slot][P][8] doubles (k_koopman_stats), and the
+// table k_koopman_nmse_table makes of them -- [P][4] per-step coefficients, then 8 doubles for the six
+// losses.  The table shares the step count's buffer, STEP_DOUBLES doubles in (the count is one int): the
+// gradient and apply kernels find it from the pointer they already take, so their argument lists do
+// not depend on the loss
+constexpr int STEP_DOUBLES = 1;
+inline size_t stat_doubles(const Plan& pl, int max_slot) { return (size_t)max_slot * pl.P * 8; }
+inline size_t tab_doubles(const Plan& pl) { return (size_t)pl.P * 4 + 8; }
+inline size_t step_bytes(const Plan& pl) { return (STEP_DOUBLES + tab_doubles(pl)) * sizeof(double); }
+
 // lifted-state index of (tile, row in tile) / of padded k index kk; -1 = padding
 inline int z_of_row(const Plan& pl, int tile, int r) {
   if (tile == 0) return r < pl.xd ? r : -1;

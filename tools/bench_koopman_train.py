@@ -2,15 +2,17 @@
 """Time the fused Koopman training step (sim_koopman_train_step) against the eager torch step it
 replaces, and run a short train() on a rollout of the project's own generator.
 
-    python tools/bench_koopman_train.py [--model DKUC|DBKN] [--batches 128,4096] [--steps 200] [--windows 7]
-                                        [--epochs 20] [--out profiles/koopman_train.json]
+    python tools/bench_koopman_train.py [--model DKUC|DBKN] [--loss mse|nmse|weighted_mse] [--batches 128,4096]
+                                        [--steps 200] [--windows 7] [--epochs 20] [--out profiles/koopman_train.json]
 
 Needs a GPU.  Per batch size, on a random [T+1, N, 13] fp32 rollout (T = 20):
 
 * fused: `KoopmanTrainer.step` (two launches, no host synchronisation between steps); with
   `--model DBKN` `BilinearKoopmanTrainer.step` on a `KoopmanBlinear` whose `H` is 0.05 randn (a zero `H`
   would time the bilinear products on zeros and let the agreement check pass without them), and the
-  default --out is profiles/koopman_train_dbkn.json;
+  default --out is profiles/koopman_train_dbkn.json; with `--loss nmse` / `weighted_mse` the trainer's loss_name
+  (nmse: four launches), the eager step's BaseLoss written out the same way, and the default --out
+  profiles/koopman_train_<loss>.json (`_dbkn_<loss>` for DBKN);
 * eager: this project's `Koopmanlinear().double()` (`KoopmanBlinear` for DBKN) on the same GPU, the section-2 loss of
   include/koopman_mpc.h written with torch ops (six encoder calls, P model steps, the MSE
   reductions), `loss.backward()` and `torch.optim.Adam.step()` -- the parent has no HIP path for
@@ -58,8 +60,18 @@ def make_net(seed=0, model="DKUC", hscale=0.05):
     return net
 
 
-def eager_loss(net, rows, idx, t0):
+def base_loss(loss, preds, labels):
+    """the reference's BaseLoss (models/losses.py:35-52), written out"""
     import torch
+    import torch.nn.functional as F
+    if loss == "nmse":
+        return F.mse_loss(preds, labels) / torch.square(labels).mean()
+    if loss == "weighted_mse":
+        return (F.mse_loss(preds[:, :3], labels[:, :3]) + 9 * F.mse_loss(preds[:, 3:], labels[:, 3:])) / 10
+    return torch.mean((preds - labels) ** 2)
+
+
+def eager_loss(net, rows, idx, t0, loss="mse"):
     w = rows[t0:t0 + P + 1].index_select(1, idx).double()
     x, u = w[:, :, UD:], w[:, :, :UD]
     beta = [GAMMA ** i for i in range(P)]
@@ -67,12 +79,12 @@ def eager_loss(net, rows, idx, t0):
     koop = pred = 0.0
     for i in range(P):
         z = net.koopman_operation(z, u[i])
-        koop = koop + beta[i] * torch.mean((z - net.x_encoder(x[i + 1])) ** 2)
-        pred = pred + beta[i] * torch.mean((net.x_decoder(z) - x[i + 1]) ** 2)
+        koop = koop + beta[i] * base_loss(loss, z, net.x_encoder(x[i + 1]))
+        pred = pred + beta[i] * base_loss(loss, net.x_decoder(z), x[i + 1])
     return (koop + pred) / sum(beta)
 
 
-def bench_batch(n, steps, windows, model="DKUC"):
+def bench_batch(n, steps, windows, model="DKUC", loss="mse"):
     import numpy as np
     import torch
     from lerobot_mujoco_sim2real_amd.control.koopman_train import BilinearKoopmanTrainer, KoopmanTrainer, params_from_net
@@ -84,13 +96,14 @@ def bench_batch(n, steps, windows, model="DKUC"):
     t0s = [int(v) for v in torch.randint(0, T - P, (steps,), generator=g)]
     net = make_net(model=model).to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=1e-3)
-    tr = (KoopmanTrainer if model == "DKUC" else BilinearKoopmanTrainer)(make_net(model=model), n, pre_length=P, gamma=GAMMA)
+    tr = (KoopmanTrainer if model == "DKUC" else BilinearKoopmanTrainer)(make_net(model=model), n, pre_length=P, gamma=GAMMA,
+                                                                          loss_name=loss)
     losses = torch.empty(6, dtype=torch.float64, device=dev)
 
     def eager(k):
         for t0 in t0s[:k]:
             opt.zero_grad(set_to_none=True)
-            eager_loss(net, rows, idx, t0).backward()
+            eager_loss(net, rows, idx, t0, loss).backward()
             opt.step()
         torch.cuda.synchronize()
 
@@ -122,7 +135,7 @@ def bench_batch(n, steps, windows, model="DKUC"):
     return rec
 
 
-def sanity_train(epochs, model="DKUC"):
+def sanity_train(epochs, model="DKUC", loss="mse"):
     import torch
     from lerobot_mujoco_sim2real_amd import mjcf
     from lerobot_mujoco_sim2real_amd.args import Args
@@ -137,7 +150,7 @@ def sanity_train(epochs, model="DKUC"):
     torch.cuda.synchronize()
     a = time.perf_counter()
     hist = train(net, data, args=_Args, epochs=epochs, batch_size=128, lr=1e-3, seed=0, eval_rollout=held,
-                 eval_interval=max(1, epochs // 4))
+                 eval_interval=max(1, epochs // 4), loss_name=loss)
     torch.cuda.synchronize()
     wall = time.perf_counter() - a
     after = MPCController(net, _Args).evaluate(held)
@@ -154,23 +167,27 @@ def main():
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--epochs", type=int, default=20)
     ap.add_argument("--model", choices=("DKUC", "DBKN"), default="DKUC")
+    ap.add_argument("--loss", choices=("mse", "nmse", "weighted_mse"), default="mse")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "koopman_train.json" if a.model == "DKUC" else "koopman_train_dbkn.json")
+        name = "koopman_train" + ("" if a.model == "DKUC" else "_dbkn") + ("" if a.loss == "mse" else "_" + a.loss)
+        a.out = os.path.join(ROOT, "profiles", name + ".json")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_koopman_train needs a GPU")
     out = dict(device=torch.cuda.get_device_name(0), layers=LAYERS, pre_length=P,
-               step=[bench_batch(int(b), a.steps, a.windows, a.model) for b in a.batches.split(",")])
+               step=[bench_batch(int(b), a.steps, a.windows, a.model, a.loss) for b in a.batches.split(",")])
     if a.model != "DKUC":
         out["model"] = a.model
+    if a.loss != "mse":
+        out["loss"] = a.loss
     for r in out["step"]:
         print(f"batch {r['batch']}: fused {r['fused_ms_per_step']:.4f} ms/step ({r['fused_ms_min']:.4f}..{r['fused_ms_max']:.4f}), "
               f"eager {r['eager_ms_per_step']:.4f} ms/step ({r['eager_ms_min']:.4f}..{r['eager_ms_max']:.4f}), "
               f"ratio {r['eager_over_fused']:.1f}x, agree {r['agree_after_3_steps']:.1e}", flush=True)
     if a.epochs > 0:
-        out["train"] = s = sanity_train(a.epochs, a.model)
+        out["train"] = s = sanity_train(a.epochs, a.model, a.loss)
         print(f"train(): {s['epochs']} epochs in {s['wall_s']:.2f} s, loss {s['first_epoch_loss']:.4e} -> {s['last_epoch_loss']:.4e}, "
               f"evaluate avg_error {s['before']['avg_error']:.4f} -> {s['after']['avg_error']:.4f}", flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -1,7 +1,7 @@
 // koopman_train_selftest.cpp — the Koopman trainer's host-side code (csrc/koopman_train_plan.h: the
 // plan of the DKUC trainer and of the bilinear DBKN one, the fragment index map, the slot gather index,
-// blob packing, the per-step argument checks) as a stand-alone program for the host sanitizers.  No
-// GPU, no HIP:
+// blob packing, the nmse workspace sizes, the per-step argument checks) as a stand-alone program for the
+// host sanitizers.  No GPU, no HIP:
 //
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all
 //       tools/koopman_train_selftest.cpp -o /tmp/koopman_train_selftest && /tmp/koopman_train_selftest
@@ -91,6 +91,18 @@ static void check_shape(std::vector<int> w, int ud, int P) {
   REQUIRE(pl.abks % 4 == 0 && pl.atks % 2 == 0);
   REQUIRE(pl.scr_stride == P * 2 * (1 + ntl) * 256 + (MAXL - 1) * 1024);
   for (int q = 0; q < pl.nparam; q++) REQUIRE(gidx[q] >= 0 && gidx[q] + 8 < pl.slot_stride + 1);
+  // the nmse workspace: every wave's [P][8] sums inside the stats buffer; the table [P][4] and the six
+  // losses behind the step count, inside its buffer and clear of the count; the table kernel's LDS row
+  for (int max_batch : {1, 16, 17, 130, 4096}) {
+    const int max_slot = (max_batch + 15) / 16;
+    REQUIRE(stat_doubles(pl, max_slot) == (size_t)max_slot * P * 8);
+    REQUIRE(((size_t)(max_slot - 1) * P + (P - 1)) * 8 + 7 < stat_doubles(pl, max_slot));
+  }
+  REQUIRE(tab_doubles(pl) == (size_t)4 * P + 8 && pl.P <= MAXP);  // (the table kernel's LDS: [MAXP][8])
+  REQUIRE(STEP_DOUBLES * sizeof(double) >= sizeof(int));
+  REQUIRE(step_bytes(pl) == (STEP_DOUBLES + tab_doubles(pl)) * sizeof(double));
+  REQUIRE((STEP_DOUBLES + (size_t)4 * (P - 1) + 3) * sizeof(double) < step_bytes(pl));  // the last coefficient
+  REQUIRE((STEP_DOUBLES + (size_t)4 * P + 5) * sizeof(double) < step_bytes(pl));        // the last loss
   // the per-step argument checks
   float rows = 0;
   const int T = P + 3;
