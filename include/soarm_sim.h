@@ -302,6 +302,20 @@ int sim_observe(sim_batch* b, const sim_state* s, float* obs, void* stream);
    int32 bits), ncon [N].  Contact order = candidate-pair order (MuJoCo's). */
 int sim_contacts(sim_batch* b, const sim_state* s, float* out, int32_t* ncon, void* stream);
 
+/* replaces mj_forward at the current state + mj_contactForce(m, d, i, f) for i < ncon: the
+   forward dynamics of the current qpos, qvel, ctrl, qacc_warmstart and qfrc_applied with the
+   batch's sim_params and the model's solver, then every contact's four pyramid edge forces
+   decoded as mju_decodePyramid does (condim 3).  A pure readout: it writes nothing into the
+   state and nothing that a later sim_step / sim_substeps reads.
+   contacts [N][SIM_MAXCON][8]  as sim_contacts writes them, or NULL
+   force    [N][SIM_MAXCON][6]  (f_normal, f_tangent1, f_tangent2) in the contact frame (mju_makeFrame
+                                of the normal), then the same force as a world vector: the force on
+                                geom2's body; geom1's body gets its negative
+   ncon     [N]
+   Past the cap the first SIM_MAXCON contacts are kept, as the step keeps them; slots >= ncon[e]
+   are zero. */
+int sim_contact_forces(sim_batch* b, const sim_state* s, float* contacts, float* force, int32_t* ncon, void* stream);
+
 /* diagnostic: geom poses + one collide pass with per-pair timing; cycles [2][npair]
    (host) = per pair, the sum over its waves of each wave's shader-clock cycles, then the
    largest single wave's.  Synchronous. */

@@ -90,6 +90,11 @@ class SOARM101VecEnv:
         obs = self.sim.step(action, self.frame_skip)
         return obs, 0.0, False, False, {}
 
+    def contact_forces(self):
+        """(contacts [n, 16, 8], force [n, 16, 6], ncon [n]) at the current state: what
+        ``mj_forward`` + ``mj_contactForce`` give (BatchSim.contact_forces)."""
+        return self.sim.contact_forces()
+
     def close(self):
         self.sim.close()
 

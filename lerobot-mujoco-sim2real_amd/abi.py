@@ -154,7 +154,7 @@ EXPORTS = [
     "sim_batch_create", "sim_batch_free", "sim_batch_set_params", "sim_reset",
     "sim_step", "sim_substeps", "sim_bias", "sim_observe", "sim_contacts", "sim_collide_profile", "sim_phase_profile", "sim_ik_dls",
     "sim_profile_begin", "sim_profile_end", "sim_rand_uniform", "sim_ik_dls_pose",
-    "sim_ik_box",
+    "sim_ik_box", "sim_contact_forces",
     "sim_model_save", "sim_model_load",
     # include/koopman_mpc.h
     "sim_koopman_create", "sim_koopman_free", "sim_koopman_encode", "sim_koopman_feedforward",
@@ -201,6 +201,7 @@ def load_lib(path=None):
     lib.sim_observe.argtypes = [vp, C.POINTER(SimState), vp, vp]
     lib.sim_bias.argtypes = [vp, C.POINTER(SimState), vp, vp]
     lib.sim_contacts.argtypes = [vp, C.POINTER(SimState), vp, vp, vp]
+    lib.sim_contact_forces.argtypes = [vp, C.POINTER(SimState), vp, vp, vp, vp]
     lib.sim_collide_profile.argtypes = [vp, C.POINTER(SimState), vp, vp]
     lib.sim_phase_profile.argtypes = [vp, ip]
     lib.sim_profile_begin.argtypes = [vp]

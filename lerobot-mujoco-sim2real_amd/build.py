@@ -14,7 +14,8 @@ import time
 from .abi import LIB_PATH, PKG_DIR
 
 SRC_DIR = os.path.join(PKG_DIR, "csrc")
-SOURCES = ["soarm_sim.hip", "koopman_mpc.hip", "koopman_train.hip", "soarm_cpu.hip", "soarm_model.hip"]
+SOURCES = ["soarm_sim.hip", "soarm_cforce.hip", "koopman_mpc.hip", "koopman_train.hip", "soarm_cpu.hip",
+           "soarm_model.hip"]
 # translation units compiled for the host only (the CPU backend, the model build: no kernels)
 HOST_ONLY = {"soarm_cpu.hip", "soarm_model.hip"}
 HEADERS = ["dmodel.h", "soarm_kernels.h", "soarm_step.h", "soarm_collide.h", "soarm_pgs.h", "soarm_rs.h", "soarm_newton.h",

@@ -94,8 +94,17 @@ int cpu_step(CpuBatch* c, const sim_state* s, const sim_params& p, const float* 
 int cpu_bias(CpuBatch* c, const sim_state* s, const sim_params& p, float* qfrc_bias);
 int cpu_observe(CpuBatch* c, const sim_state* s, float* obs);
 int cpu_contacts(CpuBatch* c, const sim_state* s, float* out, int32_t* ncon);
+int cpu_contact_forces(CpuBatch* c, const sim_state* s, const sim_params& p, float* contacts, float* force,
+                       int32_t* ncon);
 int cpu_rand_uniform(CpuBatch* c, uint64_t seed, int64_t env_offset, uint32_t counter, int k, float lo, float hi,
                      float* out);
+
+// ---- the contact-force readout's kernel (soarm_cforce.hip: k_contact_force, its own translation
+// unit): launched by sim_contact_forces after k_geom + the collide, on the collide's output
+// (cbuf, pmask; it clears the mask as k_gather does).  Returns a hipError_t as int.
+int launch_contact_force(int nf, int sol, const soarm::DModel* d_model, int n, const sim_state& st,
+                         const sim_params& pp, const float* cbuf, uint32_t* pmask, float* contacts, float* force,
+                         int32_t* ncon, void* stream);
 int cpu_ik(CpuBatch* c, const float* target, const float* target_quat, float* q, int32_t* ok, int32_t* iters,
            const sim_ik_opts& o);
 int cpu_ik_box(CpuBatch* c, int nframe, const float* target, const float* target_quat, float* q, float* q_traj,

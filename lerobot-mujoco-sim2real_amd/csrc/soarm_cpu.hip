@@ -111,6 +111,21 @@ struct Rows {
   float J[MAXR][NV], aref[MAXR], R[MAXR], fl[MAXR];
 };
 
+// contact frame (mju_makeFrame): rows normal, tangent 1, tangent 2
+inline void contact_frame(const float* nrm, float fr[9]) {
+  fr[0] = nrm[0], fr[1] = nrm[1], fr[2] = nrm[2];
+  float y[3];
+  if (fabsf(fr[1]) < 0.5f)
+    y[0] = 0, y[1] = 1, y[2] = 0;
+  else
+    y[0] = 0, y[1] = 0, y[2] = 1;
+  const float dd = dot3(fr, y);
+  y[0] -= dd * fr[0], y[1] -= dd * fr[1], y[2] -= dd * fr[2];
+  const float inv = 1.f / sqrtf(dot3(y, y));
+  fr[3] = y[0] * inv, fr[4] = y[1] * inv, fr[5] = y[2] * inv;
+  cross(fr + 6, fr, fr + 3);
+}
+
 // mj_makeConstraint in MuJoCo's row order, from the same model constants as the kernels
 // (soarm_pgs.h solve_constraints: dof_fricR/B, jnt_KB, pair_KB / tran / solimp / margin)
 template <int NA, int NF>
@@ -146,19 +161,8 @@ void make_rows(const Sim<NA, NF>& S, const CpuContact* con, int ncon, Rows<NA, N
     const CpuContact& cc = con[c];
     const int p = cc.pair, b1 = m.pair_body1[p], b2 = m.pair_body2[p];
     const float mu = S.fric >= 0.f ? S.fric : m.pair_friction[p];
-    float fr[9] = {cc.n[0], cc.n[1], cc.n[2], 0, 0, 0, 0, 0, 0};
-    {  // contact frame (mju_makeFrame)
-      float y[3];
-      if (fabsf(fr[1]) < 0.5f)
-        y[0] = 0, y[1] = 1, y[2] = 0;
-      else
-        y[0] = 0, y[1] = 0, y[2] = 1;
-      const float dd = dot3(fr, y);
-      y[0] -= dd * fr[0], y[1] -= dd * fr[1], y[2] -= dd * fr[2];
-      const float inv = 1.f / sqrtf(dot3(y, y));
-      fr[3] = y[0] * inv, fr[4] = y[1] * inv, fr[5] = y[2] * inv;
-      cross(fr + 6, fr, fr + 3);
-    }
+    float fr[9];
+    contact_frame(cc.n, fr);
     // relative translational Jacobian (body2 - body1) at the contact point, contact frame
     float jd[3][NV] = {};
     for (int side = 0; side < 2; side++) {
@@ -224,8 +228,9 @@ void mul_m(const Sim<NA, NF>& S, const float* x, float* y) {
 }
 
 // ------------------------------------------------------------------ mj_solPGS
+// frow (may be null): the solution's force per row (efc_force), for the contact-force readout
 template <int NA, int NF>
-void solve_pgs(Sim<NA, NF>& S, const Rows<NA, NF>& X) {
+void solve_pgs(Sim<NA, NF>& S, const Rows<NA, NF>& X, float* frow = nullptr) {
   constexpr int NV = Sim<NA, NF>::NV, MAXR = Rows<NA, NF>::MAXR;
   const DModel& m = *S.mp;
   const int nr = X.nr;
@@ -284,6 +289,8 @@ void solve_pgs(Sim<NA, NF>& S, const Rows<NA, NF>& X) {
     for (int r = 0; r < nr; r++) s += X.J[r][i] * f[r];
     S.fcon[i] = s;
   }
+  if (frow)
+    for (int r = 0; r < nr; r++) frow[r] = f[r];
 }
 
 // ------------------------------------------------------------------ mj_solNewton
@@ -402,7 +409,7 @@ bool chol_solve(float (&A)[N][N], float* x, const float* b) {
 }
 
 template <int NA, int NF>
-void solve_newton(Sim<NA, NF>& S, const Rows<NA, NF>& X) {
+void solve_newton(Sim<NA, NF>& S, const Rows<NA, NF>& X, float* frow = nullptr) {
   constexpr int NV = Sim<NA, NF>::NV, MAXR = Rows<NA, NF>::MAXR;
   const DModel& m = *S.mp;
   const NewtonCtx<NA, NF> C{S, X};
@@ -475,12 +482,15 @@ void solve_newton(Sim<NA, NF>& S, const Rows<NA, NF>& X) {
     bool q;
     const float f = row_force(X, r, jar[r], q);
     for (int i = 0; i < NV; i++) S.fcon[i] += X.J[r][i] * f;
+    if (frow) frow[r] = f;  // efc_force as MuJoCo derives it from qacc
   }
 }
 
 // one mj_forward after the collision: smooth dynamics, rows, solve (sets S.qacc / S.fcon)
+// edge (may be null): the 4 pyramid edge forces of every contact, [ncon][4]
 template <int NA, int NF>
-void forward_env(Sim<NA, NF>& S, int sol, const CpuContact* con, int ncon, const float* applied, int n, int e) {
+void forward_env(Sim<NA, NF>& S, int sol, const CpuContact* con, int ncon, const float* applied, int n, int e,
+                 float* edge = nullptr) {
   constexpr int NV = Sim<NA, NF>::NV;
   S.kinematics();
   S.com_crb();
@@ -494,10 +504,13 @@ void forward_env(Sim<NA, NF>& S, int sol, const CpuContact* con, int ncon, const
     for (int i = 0; i < NV; i++) S.qacc[i] = S.qacc_s[i], S.fcon[i] = 0.f;
     return;
   }
+  float frow[Rows<NA, NF>::MAXR];
   if (sol == SIM_SOL_NEWTON)
-    solve_newton(S, X);
+    solve_newton(S, X, edge ? frow : nullptr);
   else
-    solve_pgs(S, X);
+    solve_pgs(S, X, edge ? frow : nullptr);
+  if (edge)  // the contact rows are the last 4 * ncon
+    for (int k = 0; k < 4 * ncon; k++) edge[k] = frow[X.nr - 4 * ncon + k];
 }
 
 // frame_skip x mj_step of env e (mj_checkPos/Vel, collision at the substep's positions,
@@ -687,6 +700,58 @@ int cpu_contacts(CpuBatch* c, const sim_state* s, float* out, int32_t* ncon) {
         o[0] = cl[k].dist;
         for (int q = 0; q < 3; q++) o[1 + q] = cl[k].pos[q], o[4 + q] = cl[k].n[q];
         memcpy(o + 7, &cl[k].pair, 4);
+      }
+      ncon[e] = nc;
+    });
+  });
+  return SIM_OK;
+}
+
+// mj_forward at the current state + mj_contactForce of every contact (soarm_sim.h
+// sim_contact_forces): the step's own collide_env + forward_env on a local copy of the env, the
+// edge forces decoded as mju_decodePyramid does.  Writes none of the state.
+int cpu_contact_forces(CpuBatch* c, const sim_state* s, const sim_params& pp, float* contacts, float* force,
+                       int32_t* ncon) {
+  if (int rc = check(c, s)) return rc;
+  if (!force || !ncon) return soarm_set_error(SIM_E_ARG, "null output");
+  if (c->model->desc.disable_contact) return soarm_set_error(SIM_E_ARG, "model compiled with contacts disabled");
+  const sim_state st = *s;
+  const int sol = c->model->desc.solver;
+  dispatch_nf(c->model->nf, [&](auto nfc) {
+    constexpr int NF = decltype(nfc)::value;
+    parallel_envs(c->n, [&](int e) {
+      const DModel& m = c->dm;
+      Sim<6, NF> S(&m, pp.mass_scale ? pp.mass_scale[e] : 1.f, pp.friction ? pp.friction[e] : -1.f,
+                   pp.damping_scale ? pp.damping_scale[e] : 1.f);
+      load_state(S, st, c->n, e);
+      S.kinematics();
+      CpuContact cl[SIM_MAXCON];
+      int status = 0;
+      const int nc = collide_env(*c, S, e, cl, status);
+      float edge[4 * SIM_MAXCON];
+      forward_env(S, sol, cl, nc, st.qfrc_applied, c->n, e, edge);
+      for (int k = 0; k < SIM_MAXCON; k++) {
+        float* fo = force + ((size_t)e * SIM_MAXCON + k) * 6;
+        float* co = contacts ? contacts + ((size_t)e * SIM_MAXCON + k) * 8 : nullptr;
+        if (k >= nc) {
+          for (int q = 0; q < 6; q++) fo[q] = 0.f;
+          if (co)
+            for (int q = 0; q < 8; q++) co[q] = 0.f;
+          continue;
+        }
+        const float mu = S.fric >= 0.f ? S.fric : m.pair_friction[cl[k].pair];
+        float fr[9];
+        contact_frame(cl[k].n, fr);
+        const float* g = edge + 4 * k;
+        fo[0] = (g[0] + g[1]) + (g[2] + g[3]);
+        fo[1] = mu * (g[0] - g[1]);
+        fo[2] = mu * (g[2] - g[3]);
+        for (int q = 0; q < 3; q++) fo[3 + q] = fo[0] * fr[q] + fo[1] * fr[3 + q] + fo[2] * fr[6 + q];
+        if (co) {
+          co[0] = cl[k].dist;
+          for (int q = 0; q < 3; q++) co[1 + q] = cl[k].pos[q], co[4 + q] = cl[k].n[q];
+          memcpy(co + 7, &cl[k].pair, 4);
+        }
       }
       ncon[e] = nc;
     });

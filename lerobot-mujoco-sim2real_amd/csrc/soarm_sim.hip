@@ -686,6 +686,28 @@ int sim_contacts(sim_batch* b, const sim_state* s, float* out, int32_t* ncon, vo
   return SIM_OK;
 }
 
+int sim_contact_forces(sim_batch* b, const sim_state* s, float* contacts, float* force, int32_t* ncon,
+                       void* stream) {
+  const TraceRange tr_("sim_contact_forces");
+  if (int rc = check_state(b, s)) return rc;
+  if (!force || !ncon) return fail(SIM_E_ARG, "null output");
+  if (b->cpu) return cpu_contact_forces(b->cpu, s, b->params, contacts, force, ncon);
+  if (b->model->desc.disable_contact) return fail(SIM_E_ARG, "model compiled with contacts disabled");
+  hipStream_t st = (hipStream_t)stream;
+  dispatch_nf(b->model->nf, [&](auto nfc) {
+    constexpr int NA = 6, NF = decltype(nfc)::value;
+    hipLaunchKernelGGL((k_geom<NA, NF>), geom_grid(b->n), dim3(64), 0, st, b->d_model, b->n, *s,
+                       b->d_gpose);
+  });
+  if (b->model->desc.npair > 0)
+    launch_collide(b, st, nullptr);
+  HIPCHECK(hipGetLastError());
+  // (soarm_cforce.hip: its own translation unit, so this one's kernels stay as they are)
+  HIPCHECK((hipError_t)launch_contact_force(b->model->nf, b->model->desc.solver, b->d_model, b->n, *s, b->params,
+                                            b->d_cbuf, b->d_pmask, contacts, force, ncon, stream));
+  return SIM_OK;
+}
+
 int sim_collide_profile(sim_batch* b, const sim_state* s, double* cycles, void* stream) {
   if (int rc = check_state(b, s)) return rc;
   if (!cycles) return fail(SIM_E_ARG, "null output");

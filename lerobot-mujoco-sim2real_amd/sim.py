@@ -279,6 +279,39 @@ class BatchSim:
                                                   self._stream()))
         return out, nc
 
+    def contact_forces(self):
+        """``mj_forward`` at the current state + ``mj_contactForce`` of every contact
+        (``sim_contact_forces``): (contacts [n, MAXCON, 8], force [n, MAXCON, 6], ncon [n]).
+
+        contacts: as :meth:`contacts`.  force: (normal, tangent 1, tangent 2) in the contact
+        frame, then the same force as a world vector -- the force on geom2's body; geom1's body
+        gets its negative.  Slots >= ncon are zero.  A pure readout: the state, the warm start
+        and everything a later step reads stay as they are."""
+        torch = self.torch
+        out = torch.zeros((self.n, abi.MAXCON, 8), dtype=torch.float32, device=self.device)
+        frc = torch.zeros((self.n, abi.MAXCON, 6), dtype=torch.float32, device=self.device)
+        nc = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        abi.check(self.lib, self.lib.sim_contact_forces(self._batch, C.byref(self._state), _ptr(out), _ptr(frc),
+                                                        _ptr(nc), self._stream()))
+        return out, frc, nc
+
+    def net_contact_force(self, body):
+        """World-frame sum [n, 3] over each env's contacts of the contact force on `body` (an id or
+        a name): + where the body owns the pair's geom2, - where it owns geom1."""
+        torch = self.torch
+        d = self.cm.desc
+        bid = self.cm.body(body) if isinstance(body, str) else int(body)
+        if not 0 <= bid < d.nbody:
+            raise ValueError(f"body id {bid} out of range")
+        sign = np.zeros(max(d.npair, 1), dtype=np.float32)
+        for p in range(d.npair):
+            sign[p] = float(d.geom_bodyid[d.pair_geom2[p]] == bid) - float(d.geom_bodyid[d.pair_geom1[p]] == bid)
+        con, frc, nc = self.contact_forces()
+        pair = con[:, :, 7].contiguous().view(torch.int32).long().clamp_(0, max(d.npair, 1) - 1)
+        w = torch.as_tensor(sign, device=self.device)[pair]
+        w = w * (torch.arange(abi.MAXCON, device=self.device)[None, :] < nc[:, None])
+        return (frc[:, :, 3:6] * w[:, :, None]).sum(1)
+
     def collide_profile(self, with_max=False):
         """Per candidate pair, summed wave cycles of one collide pass (numpy [npair]); with_max:
         also the largest single wave's cycles per pair (the pass's critical path)."""
