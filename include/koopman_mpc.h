@@ -20,6 +20,7 @@
  *   sim_koopman_encode       Psi_o for M states (f64 MFMA encoder)
  *   sim_koopman_feedforward  Gr·r for every frame of a reference trajectory (f64 MFMA)
  *   sim_koopman_mpc_step     z0 = Psi_o(x); u0; a = clip(u0); u_prev = u0 (one launch)
+ *   sim_koopman_box_step     the DKUC step with input limits: a box QP per env (ADMM on the f64 MFMA)
  *   sim_koopman_predict      the model's multi-step open-loop prediction of recorded trajectories
  *                            and its error (evaluate(), train.py:35-87; one launch for all steps)
  *   sim_koopman_train_step   one training step of the DKUC model: loss, gradient and Adam in two
@@ -95,6 +96,61 @@ int sim_koopman_set_bilinear(sim_koopman* k, const double* A, const double* B, c
                              double q, double r);
 int sim_koopman_bilinear_step(sim_koopman* k, int n, const double* z0, const double* window, double* u_prev,
                               float* action, void* stream);
+
+/* The DKUC control step with input limits (csrc/koopman_box.hip).  sim_koopman_mpc_step solves the
+   unconstrained horizon QP and clips its first move; the plan it optimised never knew the limit.
+   This step minimises the same cost (MPC_Controler.py:80-86 / :115-127, state_full: q = 50, r = 0.5)
+   over plans whose every model input, and the input that is applied, stays in [-u_max, u_max].
+   In the model inputs w [N = H u_dim]:
+     'delta_mpc' (delta != 0)  w_t = u_prev + sum_{i<=t} du_i, |w_t| <= u_max, u0 = w_0;
+     'mpc'                     w_t = v_t, |v_t| <= u_max for t >= 1 and |v_0 + u_prev| <= u_max
+                               (the reference applies u_opt[0] + u_prev, :147), u0 = v_0 + u_prev;
+   both are  min 1/2 w'Pw - g'w,  lo <= w <= hi,  P = P(A, B, H, kind, q, r) the same for every env
+   and frame, g affine in (window, z0, u_prev).
+
+   set_box (host, once per model; independent of set_bilinear / set_model): builds P, Lhat = ||P||_inf,
+   P's extreme eigenvalues, the gains of the unconstrained minimiser wu = P^-1 g and the ADMM step
+   matrix rho (P + rho I)^-1, rho = sqrt(lambda_min lambda_max), as MFMA fragments, and uploads them.
+   opts NULL = the defaults (u_max = the controller's u_clip, tol 1e-9, max_iter 256).
+   SIM_E_MODEL (with the limit in the message): N > 64, nz > 64, an LDS plan over 160 KiB.
+   SIM_E_ARG: NULL k / A / B, u_max <= 0, tol <= 0, max_iter < 1, q or r <= 0, a bad struct header.
+   A refusal leaves every other entry point working and box_step refused.
+   sim_koopman_box_check (an entry point beside the two above, so that the refusals can be asked for
+   without a device or a handle) runs the same option and shape checks as set_box -- one pair of
+   helpers serves both -- from the desc alone; it returns SIM_OK or the code set_box would return for
+   them.  set_box first drops the state of an earlier set_box, then runs those checks.
+
+   box_step, n envs: z0 = Psi_o(x) unless z0 [nz][n] is given; window [H][nz][n] the lifted reference
+   rows k+1 .. k+H (zero past the end); u_prev [u_dim][n] in/out (u_prev <- u0); action [n][u_dim] =
+   (float)u0 (no clip: u0 is in the box); plan [H][u_dim][n] or NULL: on return the model inputs w_t;
+   warm != 0 with a plan: the plan as given (the caller passes last frame's, shifted or not) is a
+   candidate start beside the cold one, clip(wu): the iteration starts from clip(plan) where
+   res(clip(plan)) < res(clip(wu)) mu / (4 Lhat) or <= tol, i.e. where the plan is provably the closer of the two
+   (res / 2 <= ||w - w*|| <= 2 (Lhat / mu) res), else cold; ok [n], iters [n] int32 or NULL.
+   Stop test: with res(w) = w - clip(w - (P w - g) / Lhat, lo, hi) an env is done when ||res(w)||_inf <=
+   tol: ok = 1, iters = the iterations it took.  An env whose wu lies in the box returns it with iters =
+   0, warm or not, and a wave whose 16 envs all do leaves before the iteration (the matrices of the
+   iteration are not even staged when that holds for the whole workgroup).  An env that reaches
+   max_iter gets ok = 0, iters = max_iter and its last iterate, which is a projection: inside the box.
+   Deterministic; an env's result does not depend on n or on its neighbours (columns of an MFMA).
+   No allocation, copy or synchronisation: capturable in a graph.
+   SIM_E_ARG before any launch: set_box not called (or refused), NULL k / window / u_prev / action,
+   n < 0, x and z0 both NULL.  n == 0 is a no-op. */
+typedef struct sim_koopman_box_opts {
+  int32_t struct_size; /* sizeof(sim_koopman_box_opts) */
+  int32_t abi_version; /* SIM_ABI_VERSION */
+  int32_t max_iter;    /* 256 (twice the measured maximum, rounded up) */
+  int32_t _pad;
+  double u_max;        /* 0.5 */
+  double tol;          /* 1e-9 */
+} sim_koopman_box_opts;
+
+int sim_koopman_box_check(const sim_koopman_desc* desc, const sim_koopman_box_opts* opts);
+int sim_koopman_set_box(sim_koopman* k, const double* A, const double* B, int delta, double q, double r,
+                        const sim_koopman_box_opts* opts);
+int sim_koopman_box_step(sim_koopman* k, int n, const float* x, const double* z0, const double* window,
+                         double* u_prev, double* plan, int warm, float* action, int32_t* ok, int32_t* iters,
+                         void* stream);
 
 /* Open-loop prediction and its error: how well the Koopman model predicts recorded trajectories.
    This is what evaluate() (train.py:35-87) reports, through pred_and_eval_loss_old

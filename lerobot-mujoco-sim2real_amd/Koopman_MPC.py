@@ -13,7 +13,10 @@ Per frame k of a T-frame reference ``state_all_ref = [cartesian xyz, joint angle
 :class:`KoopmanMPCTracking` runs that loop for n envs on one GPU with no host round trip:
 ``sim_bias`` writes ``qfrc_applied`` in place, the reference is lifted and turned into per-frame
 feedforward terms once (the reference recomputes the same lifted rows every frame), then each
-frame is ``sim_bias`` + ``sim_koopman_mpc_step`` + ``sim_step``.  With a ``communicator``
+frame is ``sim_bias`` + ``sim_koopman_mpc_step`` + ``sim_step``.  ``constrained=True`` replaces the
+closed form and its clip by the horizon QP with the input limit in it (``sim_koopman_box_step``, DKUC):
+the lifted reference is kept, each frame's window is a view of it, and ``plan`` holds the frame's
+plan; every frame starts cold (the step's warm start is not used: measured, it saves nothing).  With a ``communicator``
 (``utility.ZMQ.ZMQCommunicator``) each frame also publishes env ``stream_env_id``'s joint angles
 as real-robot targets, as the reference does after its step (:186-190).  Past the last frame
 ``runFunc`` plays the reference's return to the model's ``home`` keyframe (:62-81, :148-183): one
@@ -30,9 +33,12 @@ class KoopmanMPCTracking:
     """n envs tracking their own reference trajectories with one MPCController."""
 
     def __init__(self, controller, model, cartesian_points, joint_angle_traj, device=0, sim=None,
-                 communicator=None, stream_env_id=0):
+                 communicator=None, stream_env_id=0, constrained=False):
         import torch
 
+        if constrained and controller.bilinear:
+            raise NotImplementedError("KoopmanMPCTracking(constrained=True) is DKUC only: the constrained step "
+                                      "does not cover a DBKN net")
         self.communicator = communicator
         self.stream_env_id = stream_env_id
 
@@ -51,7 +57,15 @@ class KoopmanMPCTracking:
         self.sim.enable_qfrc_applied()
         self.H = controller.H
         zref = controller.lift_reference(self.state_all_ref)
-        if controller.bilinear:
+        self.constrained = bool(constrained)
+        self.plan = self.ok = self.iters = None
+        if self.constrained:
+            if getattr(controller, "_box", None) is None:  # (a set_box of the caller's, with its options, stays)
+                controller.set_box()
+            self.zpad = torch.cat([zref, torch.zeros((self.H,) + zref.shape[1:], dtype=zref.dtype, device=dev)])
+            self.ff = None
+            self.plan = torch.zeros((self.H, controller.u_dim, self.n), dtype=torch.float64, device=dev)
+        elif controller.bilinear:
             # DBKN: the QP depends on each frame's lifted state, so the lifted reference is kept
             # (zero rows past the end, :199-205) and each frame solves its n QPs
             self.zpad = torch.cat([zref, torch.zeros((self.H,) + zref.shape[1:], dtype=zref.dtype, device=dev)])
@@ -87,7 +101,10 @@ class KoopmanMPCTracking:
         if k >= self.total_frames:
             return self._after_trajectory()
         self.sim.bias(out=self.sim.qfrc_applied)
-        if self.ff is None:
+        if self.constrained:  # every frame starts cold: a start from the previous plan does not help
+            _, self.ok, self.iters = self.ctl.step_box(self.state, self.zpad[k + 1:k + 1 + self.H], self.u_prev,
+                                                       self.action, plan=self.plan)
+        elif self.ff is None:
             self.ctl.step_bilinear(self.state, self.zpad[k + 1:k + 1 + self.H], self.u_prev, self.action)
         else:
             self.ctl.step(self.state, self.ff[k], self.u_prev, self.action)

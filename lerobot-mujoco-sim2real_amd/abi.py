@@ -141,6 +141,20 @@ class KoopmanTrainOpts(_Versioned):
     ]
 
 
+class KoopmanBoxOpts(_Versioned):
+    """``sim_koopman_box_opts`` (include/koopman_mpc.h): the input limit, the stop tolerance of the
+    natural residual and the iteration cap of the constrained DKUC step."""
+    _fields_ = [
+        ("struct_size", i32), ("abi_version", i32),
+        ("max_iter", i32), ("_pad", i32),
+        ("u_max", f64), ("tol", f64),
+    ]
+
+    def __init__(self, u_max=0.5, tol=1e-9, max_iter=256):
+        super().__init__()
+        self.u_max, self.tol, self.max_iter = u_max, tol, max_iter
+
+
 class SimParams(C.Structure):
     _fields_ = [("mass_scale", C.c_void_p), ("friction", C.c_void_p), ("damping_scale", C.c_void_p)]
 
@@ -160,6 +174,7 @@ EXPORTS = [
     "sim_koopman_create", "sim_koopman_free", "sim_koopman_encode", "sim_koopman_feedforward",
     "sim_koopman_mpc_step", "sim_koopman_set_bilinear", "sim_koopman_bilinear_step",
     "sim_koopman_set_model", "sim_koopman_predict",
+    "sim_koopman_box_check", "sim_koopman_set_box", "sim_koopman_box_step",
     "sim_koopman_trainer_nparam", "sim_koopman_trainer_create", "sim_koopman_trainer_free",
     "sim_koopman_trainer_get_params", "sim_koopman_trainer_set_params",
     "sim_koopman_loss_grad", "sim_koopman_train_step",
@@ -220,6 +235,9 @@ def load_lib(path=None):
     lib.sim_koopman_bilinear_step.argtypes = [vp, ip, vp, vp, vp, vp, vp]
     lib.sim_koopman_set_model.argtypes = [vp, vp, vp, vp]
     lib.sim_koopman_predict.argtypes = [vp, ip, ip, vp, ip, ip, ip, ip, ip, vp, vp, vp]
+    lib.sim_koopman_box_check.argtypes = [C.POINTER(KoopmanDesc), C.POINTER(KoopmanBoxOpts)]
+    lib.sim_koopman_set_box.argtypes = [vp, vp, vp, ip, C.c_double, C.c_double, C.POINTER(KoopmanBoxOpts)]
+    lib.sim_koopman_box_step.argtypes = [vp, ip, vp, vp, vp, vp, vp, ip, vp, vp, vp, vp]
     lib.sim_koopman_trainer_nparam.argtypes = [C.POINTER(KoopmanDesc)]
     lib.sim_koopman_trainer_create.argtypes = [C.POINTER(KoopmanDesc), vp, ip, C.POINTER(KoopmanTrainOpts), ip,
                                                C.POINTER(vp)]

@@ -14,7 +14,7 @@ import time
 from .abi import LIB_PATH, PKG_DIR
 
 SRC_DIR = os.path.join(PKG_DIR, "csrc")
-SOURCES = ["soarm_sim.hip", "soarm_cforce.hip", "koopman_mpc.hip", "koopman_train.hip", "soarm_cpu.hip",
+SOURCES = ["soarm_sim.hip", "soarm_cforce.hip", "koopman_mpc.hip", "koopman_box.hip", "koopman_train.hip", "soarm_cpu.hip",
            "soarm_model.hip"]
 # translation units compiled for the host only (the CPU backend, the model build: no kernels)
 HOST_ONLY = {"soarm_cpu.hip", "soarm_model.hip"}

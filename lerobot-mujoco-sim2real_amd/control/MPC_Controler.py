@@ -10,6 +10,9 @@ computed once on the host in float64) and every per-env evaluation runs in the H
 * :meth:`encode`       — Psi_o for a batch of states (``sim_koopman_encode``)
 * :meth:`feedforward`  — Gr · lifted reference window for every frame (``sim_koopman_feedforward``)
 * :meth:`step`         — one control step for n envs (``sim_koopman_mpc_step``)
+* :meth:`set_box` / :meth:`step_box` — the DKUC step with input limits: the horizon QP with every
+  model input and the applied input in ``[-u_max, u_max]``, solved per env (``sim_koopman_box_step``,
+  ``koopman_box.hip``; ``control/koopman.box_plan`` is the same iteration in numpy)
 * :meth:`predict` / :meth:`evaluate` — the model's open-loop prediction of a device rollout and the
   reference's evaluation metrics (``train.py:35-87``), all steps in one launch (``sim_koopman_predict``)
 
@@ -178,6 +181,56 @@ class MPCController:
                                                                _ptr(action), self._stream()))
         return action
 
+    def set_box(self, u_max=None, tol=1e-9, max_iter=None):
+        """Prepare the constrained step (``sim_koopman_set_box``): the limit u_max (default: the
+        controller's u_clip), the stop tolerance of the natural residual and the iteration cap (default:
+        the library's, 256).  DKUC only: a net with ``H`` (DBKN) has a Hessian per env and frame."""
+        if self.bilinear:
+            raise NotImplementedError("the constrained step (set_box / step_box) is DKUC only: a DBKN net's "
+                                      "Hessian differs per env and frame")
+        if self.MPC_type not in ("mpc", "delta_mpc"):
+            raise ValueError(f"MPC_type {self.MPC_type!r}: 'mpc' or 'delta_mpc'")
+        o = abi.KoopmanBoxOpts(self.u_clip if u_max is None else u_max, tol, 256 if max_iter is None else max_iter)
+        self._box = None
+        abi.check(self.lib, self.lib.sim_koopman_set_box(
+            self._h, self._Ah.ctypes.data_as(C.c_void_p), self._Bh.ctypes.data_as(C.c_void_p),
+            int(self.MPC_type == "delta_mpc"), Q_WEIGHT, R_WEIGHT, C.byref(o)))
+        self._box = (o.u_max, o.tol, o.max_iter)
+
+    def step_box(self, x, window, u_prev, action=None, z0=None, plan=None, warm=False):
+        """The constrained control step for n envs (in place): z0 = Psi_o(x) (or given [nz, n]), window
+        [H, nz, n] the lifted reference rows k+1 .. k+H (zero past the end); u_prev [u_dim, n] <- u0;
+        plan [H, u_dim, n] (optional) <- the model inputs of the plan, and with ``warm`` the start of the
+        iteration.  Returns (action [n, u_dim] float32 = u0, no clip needed; ok [n] int32: the stop test
+        was met; iters [n] int32)."""
+        torch = self.torch
+        if self.bilinear:
+            raise NotImplementedError("the constrained step (set_box / step_box) is DKUC only")
+        if getattr(self, "_box", None) is None:
+            self.set_box()
+        n = u_prev.shape[1]
+        xx = None if x is None else self._f32(x, self.in_dim)
+        if action is None:
+            action = torch.empty((n, self.u_dim), dtype=torch.float32, device=self.device)
+        ok = torch.empty((n,), dtype=torch.int32, device=self.device)
+        iters = torch.empty((n,), dtype=torch.int32, device=self.device)
+        want = {"window": (window, torch.float64, (self.H, self.Nkoopman, n)),
+                "u_prev": (u_prev, torch.float64, (self.u_dim, n)), "action": (action, torch.float32, (n, self.u_dim))}
+        if z0 is not None:
+            want["z0"] = (z0, torch.float64, (self.Nkoopman, n))
+        if plan is not None:
+            want["plan"] = (plan, torch.float64, (self.H, self.u_dim, n))
+        for name, (t, dt, shape) in want.items():
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device.type != "cuda":
+                raise ValueError(f"step_box: {name} must be a contiguous {dt} tensor of shape {shape} on {self.device}; "
+                                 f"got {t.dtype} {tuple(t.shape)} on {t.device} (contiguous: {t.is_contiguous()})")
+        if xx is not None and xx.shape[0] != n:
+            raise ValueError(f"step_box: x must hold {n} states; got {xx.shape[0]}")
+        abi.check(self.lib, self.lib.sim_koopman_box_step(self._h, n, _ptr(xx), _ptr(z0), _ptr(window), _ptr(u_prev),
+                                                          _ptr(plan), int(bool(warm)), _ptr(action), _ptr(ok),
+                                                          _ptr(iters), self._stream()))
+        return action, ok, iters
+
     def predict(self, rollout, relift=True, npos=3, want_pred=True):
         """Open-loop prediction of a rollout [T+1, N, 13] fp32 (``rollout_device``: columns
         [u | x]) in one launch, read in place (a strided or host input is first made contiguous on
@@ -223,9 +276,10 @@ class MPCController:
         self.z0 = psi
         return psi
 
-    def get_control(self, p):
+    def get_control(self, p, constrained=False):
         """(u0, a) for p = [lifted ref (H*Nkoopman, row-major); z0 (Nkoopman); u_prev (u_dim, delta_mpc)]
-        (:143-152); updates u_prev like the reference (delta_mpc: u_prev = a)."""
+        (:143-152); updates u_prev like the reference (delta_mpc: u_prev = a).  constrained: the plan
+        respects the input limit (:meth:`step_box`), so u0 is inside it and a = u0."""
         torch = self.torch
         p = np.asarray(p, np.float64).reshape(-1)
         nz, H = self.Nkoopman, self.H
@@ -235,7 +289,9 @@ class MPCController:
         dev = dict(dtype=torch.float64, device=self.device)
         up = torch.as_tensor(np.asarray(u_prev, np.float64).reshape(self.u_dim, 1), **dev).contiguous()
         zc = torch.as_tensor(z0.reshape(nz, 1), **dev).contiguous()
-        if self.bilinear:
+        if constrained:
+            self.step_box(None, torch.as_tensor(ref, **dev).reshape(H, nz, 1).contiguous(), up, z0=zc)
+        elif self.bilinear:
             self.step_bilinear(None, torch.as_tensor(ref, **dev).reshape(H, nz, 1), up, z0=zc)
         else:
             zref = torch.zeros((H + 1, nz, 1), **dev)  # frame 0 unused: the window starts at f + 1

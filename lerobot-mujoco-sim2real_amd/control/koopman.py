@@ -279,3 +279,135 @@ def condensed_gains(A, B, H, kind, q=50.0, r=0.5):
     Gz = -K @ Phi
     Gu = np.eye(nu) - K @ cu
     return Gr, Gz, Gu
+
+
+# ------------------------------------------------------------------ input-constrained MPC (DKUC)
+BOX_ALPHA = 1.6  # ADMM over-relaxation of the constrained step (csrc/koopman_box.hip uses the same)
+
+
+def box_problem(A, B, H, kind, q=50.0, r=0.5):
+    """The horizon QP of the DKUC controller in the model inputs w (N = H nu), for the step with
+    input limits (``sim_koopman_box_step``): the reference's cost (``MPC_Controler.py:80-86`` /
+    ``:115-127``, state_full) is  1/2 w' P w - g' w + const  with
+
+      'delta_mpc'  w_t = u_prev + sum_{i<=t} du_i (the inputs the model is driven with; u0 = w_0)
+      'mpc'        w_t = v_t (u0 = v_0 + u_prev)
+
+    Z = Phi z0 + Gam w for both kinds (Gam[t, s] = A^(t-s) B), the move penalty is r |D w - E0 u_prev|^2
+    (D the block first difference) for 'delta_mpc' and r |w|^2 for 'mpc', so
+    P = 2 (q Gam' Gam + r D'D | r I) depends on the model only and g = Gw rbar + Gz z0 + Gu u_prev
+    (rbar the H lifted reference rows stacked).  Returns a dict: P, Lhat = ||P||_inf, mu / lmax (P's
+    extreme eigenvalues), rho = sqrt(mu lmax) and Mrho = rho (P + rho I)^-1 (the ADMM step of
+    :func:`box_plan`), Gw [N, H nz], Gz [N, nz], Gu [N, nu], Kw / Kz / Ku = P^-1 of those (the
+    unconstrained minimiser's gains) and `shift`: 1 when block 0's bounds are shifted by -u_prev
+    ('mpc': the limit is on what is applied, v_0 + u_prev), else 0."""
+    A, B = np.asarray(A, np.float64), np.asarray(B, np.float64)
+    nz, nu = B.shape
+    N = H * nu
+    Pw = [np.eye(nz)]
+    for _ in range(H):
+        Pw.append(A @ Pw[-1])
+    Phi = np.vstack(Pw[1:])
+    Gam = np.zeros((H * nz, N))
+    for t in range(H):
+        for s in range(t + 1):
+            Gam[t * nz:(t + 1) * nz, s * nu:(s + 1) * nu] = Pw[t - s] @ B
+    Gu = np.zeros((N, nu))
+    if kind == "delta_mpc":
+        D = np.kron(np.eye(H) - np.eye(H, k=-1), np.eye(nu))
+        Rm = D.T @ D
+        Gu[:nu] = 2.0 * r * np.eye(nu)
+    elif kind == "mpc":
+        Rm = np.eye(N)
+    else:
+        raise ValueError(f"MPC_type {kind!r}: 'mpc' or 'delta_mpc'")
+    P = 2.0 * (q * Gam.T @ Gam + r * Rm)
+    P = 0.5 * (P + P.T)
+    Gw = 2.0 * q * Gam.T
+    Gz = -Gw @ Phi
+    ev = np.linalg.eigvalsh(P)
+    mu, lmax = float(ev[0]), float(ev[-1])
+    rho = float(np.sqrt(mu * lmax))
+    Kall = np.linalg.solve(P, np.hstack([Gw, Gz, Gu]))
+    return dict(P=P, Lhat=float(np.abs(P).sum(1).max()), mu=mu, lmax=lmax, rho=rho,
+                Mrho=rho * np.linalg.inv(P + rho * np.eye(N)), Gw=Gw, Gz=Gz, Gu=Gu,
+                Kw=Kall[:, :H * nz], Kz=Kall[:, H * nz:H * nz + nz], Ku=Kall[:, H * nz + nz:],
+                shift=int(kind == "mpc"), nu=nu, H=H, N=N, kind=kind)
+
+
+def box_bounds(prob, u_prev, u_max):
+    """(lo, hi) [n, N] of :func:`box_problem`'s variables for u_prev [n, nu]."""
+    u_prev = np.atleast_2d(np.asarray(u_prev, np.float64))
+    lo = np.full((u_prev.shape[0], prob["N"]), -float(u_max))
+    hi = -lo
+    if prob["shift"]:
+        lo[:, :prob["nu"]] -= u_prev
+        hi[:, :prob["nu"]] -= u_prev
+    return lo, hi
+
+
+def box_plan(prob, z0, window, u_prev, u_max=0.5, tol=1e-9, max_iter=256, plan=None):
+    """The constrained control step in float64 numpy: what ``sim_koopman_box_step`` computes, by the
+    same iteration, for n envs.  z0 [n, nz], window [n, H, nz] (lifted reference rows, zero past the
+    end), u_prev [n, nu], plan [n, N] or None (a warm start).  Returns (w [n, N], u0 [n, nu],
+    ok [n] int32, iters [n] int32).
+
+    Contract: with res(w) = w - clip(w - (P w - g) / Lhat, lo, hi), an env is done (ok = 1, iters =
+    the iterations it took) when ||res(w)||_inf <= tol; one that reaches max_iter returns its last
+    iterate (every iterate is a projection: inside the box) with ok = 0.  An env whose unconstrained
+    minimiser wu = P^-1 g lies in the box returns it with iters = 0, warm start or not.
+
+    Iteration (ADMM on  min 1/2 x'Px - g'x + I_box(z), x = z, scaled dual y, over-relaxed):
+      start  z = clip(wu), or clip(plan) where res(clip(plan)) < res(clip(wu)) mu / (4 Lhat) (or <= tol): the natural
+             residual bounds the distance to the solution from both sides, res / 2 <= ||z - z*|| <=
+             2 (Lhat / mu) res, so the plan is taken exactly when it is provably the closer start (the
+             iteration's own cold start is a good one: a plan merely near the solution does not beat it);
+             y = -(P z - g) / rho where z sits on a bound the gradient pushes
+             against, else 0 (the multiplier estimate of the start: a solution is a fixed point)
+      x = wu + Mrho (z - y - wu)      (= (P + rho I)^-1 (g + rho (z - y)));  xh = alpha x + (1 - alpha) z
+      z <- clip(xh + y);  y <- y + xh - z
+    and P z - g = P (z - wu): g itself is never formed."""
+    P, N = prob["P"], prob["N"]
+    z0 = np.atleast_2d(np.asarray(z0, np.float64))
+    n = z0.shape[0]
+    u_prev = np.atleast_2d(np.asarray(u_prev, np.float64)).reshape(n, -1)
+    s = np.hstack([np.asarray(window, np.float64).reshape(n, -1), z0, u_prev])
+    wu = s @ np.hstack([prob["Kw"], prob["Kz"], prob["Ku"]]).T
+    lo, hi = box_bounds(prob, u_prev, u_max)
+    invL, rho, alpha = 1.0 / prob["Lhat"], prob["rho"], BOX_ALPHA
+    zc = np.clip(wu, lo, hi)
+    interior = (zc == wu).all(1)
+
+    def resid(z):
+        grad = (z - wu) @ P.T
+        return grad, np.abs(z - np.clip(z - grad * invL, lo, hi)).max(1)
+
+    z = zc
+    grad, rr = resid(z)
+    if plan is not None:  # the plan is the start where it is provably the closer one (see above)
+        zp = np.clip(np.asarray(plan, np.float64).reshape(n, N), lo, hi)
+        gp, rp = resid(zp)
+        take = ((rp <= tol) | (rp < rr * (prob["mu"] / (4.0 * prob["Lhat"])))) & ~interior
+        z, grad, rr = np.where(take[:, None], zp, z), np.where(take[:, None], gp, grad), np.where(take, rp, rr)
+    done = rr <= tol
+    iters = np.zeros(n, np.int32)
+    y = np.where(((z <= lo) & (grad > 0)) | ((z >= hi) & (grad < 0)), -grad / rho, 0.0)
+    for it in range(1, int(max_iter) + 1):
+        if done.all():
+            break
+        x = wu + (z - y - wu) @ prob["Mrho"].T
+        xh = alpha * x + (1.0 - alpha) * z
+        zn = np.clip(xh + y, lo, hi)
+        yn = y + xh - zn
+        live = ~done
+        z = np.where(live[:, None], zn, z)
+        y = np.where(live[:, None], yn, y)
+        grad, rr = resid(z)
+        new = live & (rr <= tol)
+        iters[new] = it
+        done |= new
+    iters[~done] = int(max_iter)
+    u0 = z[:, :prob["nu"]] + (u_prev if prob["shift"] else 0.0)
+    if prob["shift"]:
+        u0 = np.clip(u0, -float(u_max), float(u_max))
+    return z, u0, done.astype(np.int32), iters

@@ -29,6 +29,7 @@
 #include "koopman_frag.h"
 
 int soarm_set_error(int code, const std::string& msg);  // soarm_model.hip (sim_last_error)
+void koopman_box_release(void* box);                    // koopman_box.hip
 
 namespace {
 
@@ -738,7 +739,13 @@ struct sim_koopman {
   double* d_model = nullptr;
   int model_state = 0;  // 0: not set, 1: set, 2: set_model refused the shape (SIM_E_MODEL)
   int wpw = 4;          // waves per workgroup (SOARM_KPREDICT_WAVES: 1, 2 or 4)
+  void* box = nullptr;  // the constrained step's state (sim_koopman_set_box; owned by koopman_box.hip)
 };
+
+// what koopman_box.hip needs of a handle (it includes koopman_frag.h: *kdev is its KDev)
+void koopman_handle_view(sim_koopman* k, int* device, const void** kdev, const double** frag, void*** box) {
+  *device = k->device, *kdev = &k->kd, *frag = k->d_frag, *box = &k->box;
+}
 
 #define KCHECK(x)                                                                                  \
   do {                                                                                             \
@@ -862,6 +869,7 @@ void sim_koopman_free(sim_koopman* k) {
   (void)hipFree(k->d_B);
   (void)hipFree(k->d_Hh);
   (void)hipFree(k->d_model);
+  koopman_box_release(k->box);
   delete k;
 }
 
