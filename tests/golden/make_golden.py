@@ -143,9 +143,196 @@ def contact_overflow_states(seed=5, n=1024):
     print({k: v.shape for k, v in out.items()})
 
 
+def joint_limit_states(seed=11, n=2048):
+    """tests/golden/joint_limit_states.npz: pick-scene states with active joint-limit rows, for
+    tests/joint_limits_ref.py (which documents the sets; test_joint_limits.test_fixture_census pins
+    the counts).  From the float64 oracle alone, stock PGS model; fp32-rounded qpos, qvel, warm, ctrl.
+
+    Every candidate is placed (arm pose, arm qvel, ctrl = the pose +-0.2 rad, the cube by
+    conftest.cube_qpos lowered 0.1 mm onto the table or lifted 5 cm) and then stepped 2 oracle
+    substeps, so that qvel, the warm start and the cube's contacts are those of a trajectory with the
+    limit rows in it.  A candidate is kept when its status is 0, no contact is grazing (20 um) or
+    deeper than 5 mm, and one float64 substep moves by at most SENS when qpos, qvel and the warm
+    start move by +-8 fp32 ulps (an env more sensitive than that cannot be held to a bar in fp32).
+      past    -- 1..6 joints 1.5e-4..2.5e-2 rad past a random side, qvel in +-1 rad/s, or 1..2.5
+                 rad/s out of the limit (the row that carries no force); the free joints folded
+                 clear of the table (shoulder_lift -1.2..-0.2), or, with shoulder_lift past its upper
+                 side, elbow and wrist drawn over their whole range and the census left to choose.
+                 No arm contact.  elbow_flex upper has no env, here or in `near`: from 1.6 rad on
+                 the base touches the lower arm, and at the range's end (1.69) it is 8..12 mm inside
+                 it at every shoulder and wrist pose, past the 5 mm bound; shoulder_lift upper is had
+                 free of contact with the elbow folded.  Picked in candidate order: 7 per (joint, side) with force > 0, 16
+                 with a zero-force row, 6 with all six joints limited, 10 with 4 or 5, topped up to
+                 32 at each of nlim = 1, 2, 3 and to 160 in all.
+      near    -- 1..4 joints 0.006..0.04 rad inside a random side, qvel in +-0.5 rad/s; kept when
+                 every joint is inside its range and one is within 0.045 rad.  3 per (joint, side),
+                 16 with three or more such joints, topped up to 48.
+      coupled -- a limit row, at least one arm-table or arm-cube contact, at most 6 contacts.  Two
+                 pools of contact_overflow_ref.overflow_poses (the arm lying on the table): placed as
+                 above with 1..2 joints past a side (17 of 4096 pass the depth bound: a freshly
+                 placed arm lies deep), and held 15 env-steps at the pose first, then shoulder_pan,
+                 wrist_roll or the gripper moved past a side (they leave the table contacts where
+                 they are; 378 of 2048 pass).  The 2 calmest per (joint, side) with force, by the
+                 oracle's largest constraint force, then the calmest up to 32.  No draw gave
+                 shoulder_lift (either side) or elbow_flex upper with force here: 9 of the 12 pairs.
+    """
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import contact_overflow_ref as R
+    import joint_limits_ref as J
+    from conftest import cube_qpos
+    cm = J.model()
+    orc = Oracle(cm)
+    rg = np.array([list(cm.desc.jnt_range[j]) for j in range(J.NA)])
+    SENS = R.QVEL_BARS[2] / 10
+
+    def folded(rng, m):
+        q = rng.uniform(-0.4, 0.4, (m, 6))
+        q[:, 1] = rng.uniform(-1.2, -0.2, m)
+        q[:, 5] = rng.uniform(0.0, 1.0, m)
+        return q
+
+    def push(rng, q, v, e, j, side, lo, hi, leaving):
+        """Joint j of env e to lo..hi (log-uniform) past `side` (negative: inside it)."""
+        pen = np.exp(rng.uniform(np.log(abs(lo)), np.log(abs(hi)))) * np.sign(lo)
+        q[e, j] = rg[j, side] + (pen if side else -pen)
+        if leaving:
+            q[e, j] = rg[j, side] + (1 if side else -1) * rng.uniform(8e-3, 2.2e-2)
+            v[e, j] = (-1 if side else 1) * rng.uniform(1.0, 2.5)
+
+    def evolve(rng, q, v, lifted, settled=None):
+        m = len(q)
+        full = cube_qpos(cm, m, rng, q)
+        full[:, 8] -= 1e-4
+        full[lifted, 8] += 0.05
+        st = orc.new_state(m)
+        orc.reset(st, init_qpos=full[:, :5], extra_qpos=full)
+        st["qpos"][:, :6] = q
+        if settled is not None:
+            for _ in range(15):
+                orc.step(st, q[:, :5], nthreads=8)
+            q, v = st["qpos"][:, :6].copy(), st["qvel"][:, :6].copy()
+            settled(rng, q, v)
+            st["qpos"][:, :6] = q
+        st["qvel"][:, :6] = v
+        st["ctrl"][:] = np.clip(q + rng.uniform(-0.2, 0.2, (m, 6)), rg[:, 0], rg[:, 1])
+        orc.step(st, None, nsub=2, nthreads=8)
+        sticky = st["status"].copy()
+        st = R.f32(st)
+        st["status"][:] = 0
+        st["ncon"][:] = 0
+        cen = J.census(cm, orc, st)
+        ok = (cen["status"] == 0) & (sticky == 0) & np.isfinite(cen["qvel"]).all(1)
+        ok &= (cen["graze"] > R.GRAZING) & (cen["deepest"] > -R.DEEPEST)
+        return st, cen, ok, J.sensitivity(orc, st, cen["qvel"], seed=seed + 1)
+
+    def chooser(ok):
+        pick = []
+
+        def add(mask, k):
+            ids = [int(i) for i in np.flatnonzero(mask & ok) if i not in pick]
+            pick.extend(ids[:max(0, k)])
+        return pick, add
+
+    # ---- past
+    rng = np.random.default_rng(seed)
+    q, v = folded(rng, n), rng.uniform(-1, 1, (n, 6))
+    nk = rng.choice([1, 2, 3, 4, 5, 6], n, p=[0.22, 0.22, 0.22, 0.1, 0.08, 0.16])
+    for e in range(n):
+        js = rng.choice(6, nk[e], replace=False)
+        sides = rng.integers(0, 2, 6)
+        if 1 in js and sides[1] == 1:  # shoulder_lift upper: the arm reaches down to the table
+            q[e, 2:4] = rng.uniform(rg[2:4, 0] + 0.1, rg[2:4, 1] - 0.1)
+        for j in js:
+            push(rng, q, v, e, j, sides[j], 1.5e-4, 2.5e-2, leaving=rng.random() < 0.15)
+    st, cen, ok, sens = evolve(rng, q, v, rng.random(n) < 0.5)
+    viol = np.where(cen["present"], -cen["dist"], np.nan)
+    ok &= (cen["nlim"] >= 1) & (cen["ncon"] == cen["nblk"]) & np.isin(cen["ncon"], (0, 4)) & (sens <= SENS)
+    ok &= (np.nan_to_num(viol, nan=1e-3) >= J.VIOL[0]).all((1, 2)) & (np.nan_to_num(viol, nan=1e-3) <= J.VIOL[1]).all((1, 2))
+    active = cen["present"] & (cen["force"] > 0)
+    idle = (cen["present"] & (cen["force"] == 0)).any((1, 2))
+    pick, add = chooser(ok)
+    for j in range(6):
+        for s in range(2):
+            add(active[:, j, s] & (cen["nlim"] <= 3), 7)
+            add(active[:, j, s], 7 - int(active[pick, j, s].sum()))
+    add(idle, 16 - int(idle[pick].sum()))
+    add(cen["nlim"] == 6, 6 - int((cen["nlim"][pick] == 6).sum()))
+    add((cen["nlim"] == 4) | (cen["nlim"] == 5), 10 - int(np.isin(cen["nlim"][pick], (4, 5)).sum()))
+    for k in (1, 2, 3):
+        add(cen["nlim"] == k, 32 - int((cen["nlim"][pick] == k).sum()))
+    add(np.ones(n, bool), 160 - len(pick))
+    print("past: candidates", int(ok.sum()), "of", n, "picked", len(pick), "nlim", np.bincount(cen["nlim"][pick]),
+          "active per pair", active[pick].sum(0).ravel(), "idle", int(idle[pick].sum()), "ncon", np.bincount(cen["ncon"][pick]),
+          "sens max", sens[pick].max(), "force max", cen["force"][pick].max())
+    past = R.take(st, sorted(pick))
+    # ---- near
+    rng = np.random.default_rng(seed + 2)
+    m = n // 4
+    q, v = folded(rng, m), rng.uniform(-0.5, 0.5, (m, 6))
+    for e in range(m):
+        for j in rng.choice(6, rng.integers(1, 5), replace=False):
+            push(rng, q, v, e, j, rng.integers(0, 2), -0.006, -0.04, leaving=False)
+    st, cen, ok, sens = evolve(rng, q, v, rng.random(m) < 0.5)
+    close = (cen["dist"] < J.NEAR)
+    ok &= (cen["dist"] > 0).all((1, 2)) & close.any((1, 2)) & (cen["nlim"] == 0) & (sens <= SENS)
+    ok &= (cen["ncon"] == cen["nblk"]) & np.isin(cen["ncon"], (0, 4))
+    pick, add = chooser(ok)
+    for j in range(6):
+        for s in range(2):
+            add(close[:, j, s], 3)
+    add(close.sum((1, 2)) >= 3, 16 - int((close[pick].sum((1, 2)) >= 3).sum()))
+    add(np.ones(m, bool), 48 - len(pick))
+    print("near: candidates", int(ok.sum()), "of", m, "picked", len(pick), "close per pair", close[pick].sum(0).ravel(),
+          "3+", int((close[pick].sum((1, 2)) >= 3).sum()), "ncon", np.bincount(cen["ncon"][pick]))
+    near = R.take(st, sorted(pick))
+    # ---- coupled: A, placed like the others; B, held 15 env-steps at the pose first (the arm settles
+    # on the table), then shoulder_pan, wrist_roll or the gripper moved past a side
+    rng = np.random.default_rng(seed + 3)
+    m = 2 * n
+    q, v = R.overflow_poses(rng, m), rng.uniform(-0.5, 0.5, (m, 6))
+    for e in range(m):
+        for j in rng.choice(6, rng.integers(1, 3), replace=False):
+            push(rng, q, v, e, j, 1 if j == 1 else rng.integers(0, 2), 1.5e-4, 2.5e-2, leaving=False)
+    A = evolve(rng, q, v, np.zeros(m, bool))
+
+    def moved(rng, q, v):
+        for e in range(len(q)):
+            for j in rng.choice([0, 4, 5], rng.integers(1, 3), replace=False):
+                push(rng, q, v, e, j, rng.integers(0, 2), 1.5e-4, 2.5e-2, leaving=False)
+                if v[e, j] == 0.0:
+                    v[e, j] = rng.uniform(-0.5, 0.5)
+    B = evolve(rng, R.overflow_poses(rng, n), np.zeros((n, 6)), np.zeros(n, bool), settled=moved)
+    st = R.concat(A[0], B[0])
+    cen = {k: np.concatenate([A[1][k], B[1][k]]) for k in A[1]}
+    ok, sens = np.concatenate([A[2], B[2]]), np.concatenate([A[3], B[3]])
+    ok &= (cen["nlim"] >= 1) & (cen["ncon"] > cen["nblk"]) & (cen["ncon"] <= R.LDS_CON) & (sens <= SENS)
+    ok &= cen["ncon_step"] == cen["ncon"]
+    active = cen["present"] & (cen["force"] > 0)
+    calmest = np.argsort(cen["fmax"], kind="stable")
+    pick = []
+    for j in range(6):
+        for s in range(2):
+            pick.extend([int(i) for i in calmest if ok[i] and active[i, j, s] and i not in pick][:2])
+    pick.extend([int(i) for i in calmest if ok[i] and i not in pick][:32 - len(pick)])
+    print("coupled: candidates", int(ok[:m].sum()), "of", m, "placed,", int(ok[m:].sum()), "of", n, "settled; picked", len(pick),
+          "nlim", np.bincount(cen["nlim"][pick]), "ncon", np.bincount(cen["ncon"][pick]), "arm contacts",
+          np.bincount((cen["ncon"] - cen["nblk"])[pick]), "active per pair", active[pick].sum(0).ravel(),
+          "fmax", cen["fmax"][pick].max(), "sens max", sens[pick].max())
+    coupled = R.take(st, sorted(pick))
+    out = {}
+    for name, s in (("past", past), ("near", near), ("coupled", coupled)):
+        for k in R.KEYS:
+            out[f"{name}_{k}"] = s[k].astype(np.float32)
+    np.savez_compressed(os.path.join(HERE, "joint_limit_states.npz"), **out)
+    print({k: v.shape for k, v in out.items()})
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["contact_overflow"]:
         contact_overflow_states()
+    elif sys.argv[1:] == ["joint_limit_states"]:
+        joint_limit_states()
     else:
         main()
         contact_overflow_states()
+        joint_limit_states()
