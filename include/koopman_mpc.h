@@ -21,6 +21,8 @@
  *   sim_koopman_feedforward  Gr·r for every frame of a reference trajectory (f64 MFMA)
  *   sim_koopman_mpc_step     z0 = Psi_o(x); u0; a = clip(u0); u_prev = u0 (one launch)
  *   sim_koopman_box_step     the DKUC step with input limits: a box QP per env (ADMM on the f64 MFMA)
+ *   sim_koopman_bilinear_box_step  the same for the bilinear DBKN model: a box QP with its own Hessian
+ *                            per env and frame (projected Gauss-Seidel in registers, one wave per env)
  *   sim_koopman_predict      the model's multi-step open-loop prediction of recorded trajectories
  *                            and its error (evaluate(), train.py:35-87; one launch for all steps)
  *   sim_koopman_train_step   one training step of the DKUC model: loss, gradient and Adam in two
@@ -151,6 +153,37 @@ int sim_koopman_set_box(sim_koopman* k, const double* A, const double* B, int de
 int sim_koopman_box_step(sim_koopman* k, int n, const float* x, const double* z0, const double* window,
                          double* u_prev, double* plan, int warm, float* action, int32_t* ok, int32_t* iters,
                          void* stream);
+
+/* The DBKN control step with input limits (csrc/koopman_mpc.hip, k_bilinear_box): the problem of
+   sim_koopman_box_step above -- the same kinds, bounds and u0 -- with B_total = B + sum_j z0_j Hhat_j
+   in place of B, so P = P_e differs per env and frame and nothing of it can be prepared on the host.
+   One wave per env builds P_e as sim_koopman_bilinear_step builds its Hessian and solves the box QP by
+   projected Gauss-Seidel in registers, from w = clip(0), in the order of the time blocks from the last
+   to the first.  There is no factorisation: an env whose unconstrained minimiser lies inside the box
+   is iterated like every other (iters > 0, solved to tol), unlike box_step's iters = 0.
+
+   set_bilinear_box runs after sim_koopman_set_bilinear and takes that call's A, B, Hhat, kind, q and
+   r; opts NULL = the defaults (u_max = the controller's u_clip, tol 1e-9, max_iter 128: DESIGN.md
+   section 5, twice the measured maximum of 61 sweeps, rounded up).
+   SIM_E_ARG: NULL k, set_bilinear not called, u_max <= 0, tol <= 0, max_iter < 1, a bad struct header.
+   The kernel runs on bilinear_step's LDS plan and on fewer registers, so every shape set_bilinear
+   accepts is accepted (no SIM_E_MODEL of its own).  A refusal leaves bilinear_box_step refused and
+   every other entry point working; a later set_bilinear drops the box state.
+
+   bilinear_box_step, n envs: z0 [nz][n], window [H][nz][n], u_prev [u_dim][n] in/out (u_prev <- u0) as
+   bilinear_step; action [n][u_dim] = (float)u0 (no clip: u0 is in the box); plan [H][u_dim][n] or
+   NULL: on return the model inputs w_t in natural order ('mpc': v_t); ok [n], iters [n] int32 or NULL.
+   Stop test, after every sweep: res(w) = w - clip(w - (P_e w - g_e) / Lhat_e, lo, hi), Lhat_e =
+   ||P_e||_inf; done when ||res||_inf <= tol: ok = 1, iters = the sweeps it took (>= 1).  An env that
+   reaches max_iter gets ok = 0, iters = max_iter and its last iterate, which is a projection: inside
+   the box.  There is no warm start.  Deterministic; an env's result does not depend on n or on its
+   neighbours (one wave per env).  No allocation, copy or synchronisation: capturable in a graph.
+   SIM_E_ARG before any launch: set_bilinear_box not called (or refused), NULL k / z0 / window /
+   u_prev / action, n < 0.  n == 0 is a no-op. */
+int sim_koopman_set_bilinear_box(sim_koopman* k, const sim_koopman_box_opts* opts);
+int sim_koopman_bilinear_box_step(sim_koopman* k, int n, const double* z0, const double* window,
+                                  double* u_prev, double* plan, float* action,
+                                  int32_t* ok, int32_t* iters, void* stream);
 
 /* Open-loop prediction and its error: how well the Koopman model predicts recorded trajectories.
    This is what evaluate() (train.py:35-87) reports, through pred_and_eval_loss_old

@@ -16,7 +16,8 @@ feedforward terms once (the reference recomputes the same lifted rows every fram
 frame is ``sim_bias`` + ``sim_koopman_mpc_step`` + ``sim_step``.  ``constrained=True`` replaces the
 closed form and its clip by the horizon QP with the input limit in it (``sim_koopman_box_step``, DKUC):
 the lifted reference is kept, each frame's window is a view of it, and ``plan`` holds the frame's
-plan; every frame starts cold (the step's warm start is not used: measured, it saves nothing).  With a ``communicator``
+plan; every frame starts cold (the step's warm start is not used: measured, it saves nothing).  A DBKN
+controller on which ``set_box_bilinear()`` was called runs ``sim_koopman_bilinear_box_step`` instead.  With a ``communicator``
 (``utility.ZMQ.ZMQCommunicator``) each frame also publishes env ``stream_env_id``'s joint angles
 as real-robot targets, as the reference does after its step (:186-190).  Past the last frame
 ``runFunc`` plays the reference's return to the model's ``home`` keyframe (:62-81, :148-183): one
@@ -36,9 +37,10 @@ class KoopmanMPCTracking:
                  communicator=None, stream_env_id=0, constrained=False):
         import torch
 
-        if constrained and controller.bilinear:
-            raise NotImplementedError("KoopmanMPCTracking(constrained=True) is DKUC only: the constrained step "
-                                      "does not cover a DBKN net")
+        self.box_bilinear = bool(constrained and controller.bilinear)
+        if self.box_bilinear and getattr(controller, "_box_bilinear", None) is None:
+            raise NotImplementedError("KoopmanMPCTracking(constrained=True) is DKUC only unless set_box_bilinear() "
+                                      "has been called on the DBKN controller")
         self.communicator = communicator
         self.stream_env_id = stream_env_id
 
@@ -60,7 +62,8 @@ class KoopmanMPCTracking:
         self.constrained = bool(constrained)
         self.plan = self.ok = self.iters = None
         if self.constrained:
-            if getattr(controller, "_box", None) is None:  # (a set_box of the caller's, with its options, stays)
+            # (a set_box of the caller's, with its options, stays; a DBKN controller was prepared by the caller)
+            if not self.box_bilinear and getattr(controller, "_box", None) is None:
                 controller.set_box()
             self.zpad = torch.cat([zref, torch.zeros((self.H,) + zref.shape[1:], dtype=zref.dtype, device=dev)])
             self.ff = None
@@ -101,7 +104,10 @@ class KoopmanMPCTracking:
         if k >= self.total_frames:
             return self._after_trajectory()
         self.sim.bias(out=self.sim.qfrc_applied)
-        if self.constrained:  # every frame starts cold: a start from the previous plan does not help
+        if self.box_bilinear:  # DBKN: the per-env box QP (step_box_bilinear has no warm start)
+            _, self.ok, self.iters = self.ctl.step_box_bilinear(self.state, self.zpad[k + 1:k + 1 + self.H], self.u_prev,
+                                                                self.action, plan=self.plan)
+        elif self.constrained:  # every frame starts cold: a start from the previous plan does not help
             _, self.ok, self.iters = self.ctl.step_box(self.state, self.zpad[k + 1:k + 1 + self.H], self.u_prev,
                                                        self.action, plan=self.plan)
         elif self.ff is None:

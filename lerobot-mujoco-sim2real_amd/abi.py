@@ -175,6 +175,7 @@ EXPORTS = [
     "sim_koopman_mpc_step", "sim_koopman_set_bilinear", "sim_koopman_bilinear_step",
     "sim_koopman_set_model", "sim_koopman_predict",
     "sim_koopman_box_check", "sim_koopman_set_box", "sim_koopman_box_step",
+    "sim_koopman_set_bilinear_box", "sim_koopman_bilinear_box_step",
     "sim_koopman_trainer_nparam", "sim_koopman_trainer_create", "sim_koopman_trainer_free",
     "sim_koopman_trainer_get_params", "sim_koopman_trainer_set_params",
     "sim_koopman_loss_grad", "sim_koopman_train_step",
@@ -238,6 +239,8 @@ def load_lib(path=None):
     lib.sim_koopman_box_check.argtypes = [C.POINTER(KoopmanDesc), C.POINTER(KoopmanBoxOpts)]
     lib.sim_koopman_set_box.argtypes = [vp, vp, vp, ip, C.c_double, C.c_double, C.POINTER(KoopmanBoxOpts)]
     lib.sim_koopman_box_step.argtypes = [vp, ip, vp, vp, vp, vp, vp, ip, vp, vp, vp, vp]
+    lib.sim_koopman_set_bilinear_box.argtypes = [vp, C.POINTER(KoopmanBoxOpts)]
+    lib.sim_koopman_bilinear_box_step.argtypes = [vp, ip, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.sim_koopman_trainer_nparam.argtypes = [C.POINTER(KoopmanDesc)]
     lib.sim_koopman_trainer_create.argtypes = [C.POINTER(KoopmanDesc), vp, ip, C.POINTER(KoopmanTrainOpts), ip,
                                                C.POINTER(vp)]

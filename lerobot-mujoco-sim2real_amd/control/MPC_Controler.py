@@ -13,6 +13,9 @@ computed once on the host in float64) and every per-env evaluation runs in the H
 * :meth:`set_box` / :meth:`step_box` — the DKUC step with input limits: the horizon QP with every
   model input and the applied input in ``[-u_max, u_max]``, solved per env (``sim_koopman_box_step``,
   ``koopman_box.hip``; ``control/koopman.box_plan`` is the same iteration in numpy)
+* :meth:`set_box_bilinear` / :meth:`step_box_bilinear` — the same for a DBKN net, whose Hessian
+  differs per env and frame: projected Gauss-Seidel per env (``sim_koopman_bilinear_box_step``,
+  ``koopman_mpc.hip`` ``k_bilinear_box``; ``control/koopman.box_plan_bilinear`` in numpy)
 * :meth:`predict` / :meth:`evaluate` — the model's open-loop prediction of a device rollout and the
   reference's evaluation metrics (``train.py:35-87``), all steps in one launch (``sim_koopman_predict``)
 
@@ -187,7 +190,7 @@ class MPCController:
         the library's, 256).  DKUC only: a net with ``H`` (DBKN) has a Hessian per env and frame."""
         if self.bilinear:
             raise NotImplementedError("the constrained step (set_box / step_box) is DKUC only: a DBKN net's "
-                                      "Hessian differs per env and frame")
+                                      "Hessian differs per env and frame; use set_box_bilinear / step_box_bilinear")
         if self.MPC_type not in ("mpc", "delta_mpc"):
             raise ValueError(f"MPC_type {self.MPC_type!r}: 'mpc' or 'delta_mpc'")
         o = abi.KoopmanBoxOpts(self.u_clip if u_max is None else u_max, tol, 256 if max_iter is None else max_iter)
@@ -205,7 +208,8 @@ class MPCController:
         was met; iters [n] int32)."""
         torch = self.torch
         if self.bilinear:
-            raise NotImplementedError("the constrained step (set_box / step_box) is DKUC only")
+            raise NotImplementedError("the constrained step (set_box / step_box) is DKUC only; a DBKN net has "
+                                      "set_box_bilinear / step_box_bilinear")
         if getattr(self, "_box", None) is None:
             self.set_box()
         n = u_prev.shape[1]
@@ -229,6 +233,56 @@ class MPCController:
         abi.check(self.lib, self.lib.sim_koopman_box_step(self._h, n, _ptr(xx), _ptr(z0), _ptr(window), _ptr(u_prev),
                                                           _ptr(plan), int(bool(warm)), _ptr(action), _ptr(ok),
                                                           _ptr(iters), self._stream()))
+        return action, ok, iters
+
+    def set_box_bilinear(self, u_max=None, tol=1e-9, max_iter=None):
+        """Prepare the constrained DBKN step (``sim_koopman_set_bilinear_box``): the limit u_max
+        (default: the controller's u_clip), the stop tolerance of the natural residual and the sweep cap
+        (default: the library's, 128).  DBKN only: a DKUC net has :meth:`set_box`."""
+        if not self.bilinear:
+            raise NotImplementedError("set_box_bilinear / step_box_bilinear are DBKN only: a DKUC net's constrained "
+                                      "step is set_box / step_box")
+        if self.MPC_type not in ("mpc", "delta_mpc"):
+            raise ValueError(f"MPC_type {self.MPC_type!r}: 'mpc' or 'delta_mpc'")
+        o = abi.KoopmanBoxOpts(self.u_clip if u_max is None else u_max, tol, 128 if max_iter is None else max_iter)
+        self._box_bilinear = None
+        abi.check(self.lib, self.lib.sim_koopman_set_bilinear_box(self._h, C.byref(o)))
+        self._box_bilinear = (o.u_max, o.tol, o.max_iter)
+
+    def step_box_bilinear(self, x, window, u_prev, action=None, z0=None, plan=None):
+        """The constrained DBKN control step for n envs (in place): z0 = Psi_o(x) (or given [nz, n]),
+        window [H, nz, n] the lifted reference rows k+1 .. k+H (zero past the end); u_prev [u_dim, n] <-
+        u0; plan [H, u_dim, n] (optional) <- the model inputs of the plan.  Every call starts cold.
+        Returns (action [n, u_dim] float32 = u0, no clip needed; ok [n] int32: the stop test was met;
+        iters [n] int32: the sweeps)."""
+        torch = self.torch
+        if not self.bilinear:
+            raise NotImplementedError("set_box_bilinear / step_box_bilinear are DBKN only: a DKUC net's constrained "
+                                      "step is set_box / step_box")
+        if getattr(self, "_box_bilinear", None) is None:
+            self.set_box_bilinear()
+        if z0 is None:
+            z0 = self.encode(x)
+        n = u_prev.shape[1]
+        if action is None:
+            action = torch.empty((n, self.u_dim), dtype=torch.float32, device=self.device)
+        z0 = z0.contiguous()
+        window = window.contiguous()
+        ok = torch.empty((n,), dtype=torch.int32, device=self.device)
+        iters = torch.empty((n,), dtype=torch.int32, device=self.device)
+        dev = self.device
+        want = {"z0": (z0, torch.float64, (self.Nkoopman, n)), "window": (window, torch.float64, (self.H, self.Nkoopman, n)),
+                "u_prev": (u_prev, torch.float64, (self.u_dim, n)), "action": (action, torch.float32, (n, self.u_dim))}
+        if plan is not None:
+            want["plan"] = (plan, torch.float64, (self.H, self.u_dim, n))
+        for name, (t, dt, shape) in want.items():
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device.type != "cuda" or \
+                    (dev.index is not None and t.device.index != dev.index):
+                raise ValueError(f"step_box_bilinear: {name} must be a contiguous {dt} tensor of shape {shape} on {dev}; "
+                                 f"got {t.dtype} {tuple(t.shape)} on {t.device} (contiguous: {t.is_contiguous()})")
+        abi.check(self.lib, self.lib.sim_koopman_bilinear_box_step(self._h, n, _ptr(z0), _ptr(window), _ptr(u_prev),
+                                                                   _ptr(plan), _ptr(action), _ptr(ok), _ptr(iters),
+                                                                   self._stream()))
         return action, ok, iters
 
     def predict(self, rollout, relift=True, npos=3, want_pred=True):
@@ -279,7 +333,8 @@ class MPCController:
     def get_control(self, p, constrained=False):
         """(u0, a) for p = [lifted ref (H*Nkoopman, row-major); z0 (Nkoopman); u_prev (u_dim, delta_mpc)]
         (:143-152); updates u_prev like the reference (delta_mpc: u_prev = a).  constrained: the plan
-        respects the input limit (:meth:`step_box`), so u0 is inside it and a = u0."""
+        respects the input limit (:meth:`step_box`; a DBKN controller on which :meth:`set_box_bilinear`
+        was called: :meth:`step_box_bilinear`), so u0 is inside it and a = u0."""
         torch = self.torch
         p = np.asarray(p, np.float64).reshape(-1)
         nz, H = self.Nkoopman, self.H
@@ -289,7 +344,9 @@ class MPCController:
         dev = dict(dtype=torch.float64, device=self.device)
         up = torch.as_tensor(np.asarray(u_prev, np.float64).reshape(self.u_dim, 1), **dev).contiguous()
         zc = torch.as_tensor(z0.reshape(nz, 1), **dev).contiguous()
-        if constrained:
+        if constrained and self.bilinear and getattr(self, "_box_bilinear", None) is not None:
+            self.step_box_bilinear(None, torch.as_tensor(ref, **dev).reshape(H, nz, 1).contiguous(), up, z0=zc)
+        elif constrained:
             self.step_box(None, torch.as_tensor(ref, **dev).reshape(H, nz, 1).contiguous(), up, z0=zc)
         elif self.bilinear:
             self.step_bilinear(None, torch.as_tensor(ref, **dev).reshape(H, nz, 1), up, z0=zc)

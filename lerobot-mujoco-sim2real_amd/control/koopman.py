@@ -411,3 +411,82 @@ def box_plan(prob, z0, window, u_prev, u_max=0.5, tol=1e-9, max_iter=256, plan=N
     if prob["shift"]:
         u0 = np.clip(u0, -float(u_max), float(u_max))
     return z, u0, done.astype(np.int32), iters
+
+
+# ------------------------------------------------------------------ input-constrained MPC (DBKN)
+def box_plan_bilinear(A, B, Hhat, z0, window, u_prev, kind, H, u_max=0.5, tol=1e-9, max_iter=128, q=50.0, r=0.5):
+    """The constrained DBKN control step in float64 numpy: what ``sim_koopman_bilinear_box_step``
+    computes (``koopman_mpc.hip`` ``k_bilinear_box``), by the same iteration, for n envs.  A [nz, nz],
+    B [nz, nu], Hhat [nz(j), nz, nu], z0 [n, nz], window [n, H, nz] (lifted reference rows, zero past the
+    end), u_prev [n, nu].  Returns (w [n, N] the model inputs in natural order, u0 [n, nu], ok [n] int32,
+    iters [n] int32).
+
+    Per env, with B_total = B + Σ_j z0_j Ĥ_j and Gam[t, s] = A^(t-s) B_total, the problem of
+    :func:`box_problem` in the kernel's scale (half of it):  min 1/2 w'P w - g'w,  lo <= w <= hi,
+    P = q Gam'Gam + r (D'D | I),  g = q Gam'(rbar - Phi z0) + r u_prev on block 0 ('delta_mpc').
+
+    Iteration: projected Gauss-Seidel from w = clip(0) with the gradient gr = P w - g maintained; a sweep
+    visits the entries in the kernel's lane order -- the time blocks from the last to the first, the
+    inputs of a block in order -- and step i does  wn = clip(w_i - gr_i / P_ii), gr += P[:, i] (wn - w_i),
+    w_i = wn.  Stop test after every sweep: res = w - clip(w - gr / Lhat, lo, hi), Lhat = ||P||_inf of
+    the env, done when ||res||_inf <= tol: ok = 1, iters = the sweeps it took (>= 1: there is no
+    factorisation, so an env whose unconstrained minimiser is interior is iterated too).  At max_iter:
+    ok = 0, iters = max_iter, the last iterate (every entry a projection: inside the box)."""
+    if kind not in ("mpc", "delta_mpc"):
+        raise ValueError(f"MPC_type {kind!r}: 'mpc' or 'delta_mpc'")
+    A, B, Hhat = np.asarray(A, np.float64), np.asarray(B, np.float64), np.asarray(Hhat, np.float64)
+    nz, nu = B.shape
+    N = H * nu
+    z0 = np.atleast_2d(np.asarray(z0, np.float64))
+    n = z0.shape[0]
+    u_prev = np.atleast_2d(np.asarray(u_prev, np.float64)).reshape(n, nu)
+    rbar = np.asarray(window, np.float64).reshape(n, H, nz)
+    Bt = B[None] + np.einsum("nj,jik->nik", z0, Hhat)                      # [n, nz, nu]
+    Pw = [np.eye(nz)]
+    for _ in range(H):
+        Pw.append(A @ Pw[-1])
+    Mk = np.stack([Pw[k] @ Bt for k in range(H)], 1)                        # A^k B_total [n, H, nz, nu]
+    Gam = np.zeros((n, H, nz, H, nu))
+    for t in range(H):
+        for s in range(t + 1):
+            Gam[:, t, :, s, :] = Mk[:, t - s]
+    Gam = Gam.reshape(n, H * nz, N)
+    e = rbar - np.stack([z0 @ Pw[t + 1].T for t in range(H)], 1)            # ref_t - A^(t+1) z0
+    g = q * np.einsum("nka,nk->na", Gam, e.reshape(n, H * nz))
+    if kind == "delta_mpc":
+        D = np.kron(np.eye(H) - np.eye(H, k=-1), np.eye(nu))
+        Rm = D.T @ D
+        g[:, :nu] += r * u_prev
+    else:
+        Rm = np.eye(N)
+    P = q * np.einsum("nka,nkb->nab", Gam, Gam) + r * Rm[None]
+    P = 0.5 * (P + P.transpose(0, 2, 1))
+    lo = np.full((n, N), -float(u_max))
+    hi = -lo
+    if kind == "mpc":
+        lo[:, :nu] -= u_prev
+        hi[:, :nu] -= u_prev
+    order = [(H - 1 - a // nu) * nu + a % nu for a in range(N)]             # lane a -> natural index
+    idg = 1.0 / np.einsum("nii->ni", P)
+    ilh = 1.0 / np.abs(P).sum(2).max(1)
+    w = np.clip(np.zeros((n, N)), lo, hi)
+    gr = np.einsum("nab,nb->na", P, w) - g
+    live = np.ones(n, bool)
+    iters = np.zeros(n, np.int32)
+    for it in range(1, int(max_iter) + 1):
+        for i in order:
+            wn = np.clip(w[:, i] - gr[:, i] * idg[:, i], lo[:, i], hi[:, i])
+            d = np.where(live, wn - w[:, i], 0.0)
+            w[:, i] = np.where(live, wn, w[:, i])
+            gr += P[:, :, i] * d[:, None]
+        res = np.abs(w - np.clip(w - gr * ilh[:, None], lo, hi)).max(1)
+        new = live & (res <= tol)
+        iters[new] = it
+        live &= ~new
+        if not live.any():
+            break
+    iters[live] = int(max_iter)
+    u0 = w[:, :nu].copy()
+    if kind == "mpc":
+        u0 = np.clip(u0 + u_prev, -float(u_max), float(u_max))
+    return w, u0, (~live).astype(np.int32), iters

@@ -381,6 +381,9 @@ int check_shape(int nz, int nu, int H) {
 
 }  // namespace
 
+// the option checks, for sim_koopman_set_bilinear_box (koopman_mpc.hip): one helper serves both steps
+int koopman_box_check_opts(const sim_koopman_box_opts* opts) { return check_opts(opts); }
+
 void koopman_box_release(void* box) {
   KBox* b = static_cast<KBox*>(box);
   if (!b) return;

@@ -30,6 +30,7 @@
 
 int soarm_set_error(int code, const std::string& msg);  // soarm_model.hip (sim_last_error)
 void koopman_box_release(void* box);                    // koopman_box.hip
+int koopman_box_check_opts(const sim_koopman_box_opts* opts);  // koopman_box.hip
 
 namespace {
 
@@ -240,14 +241,42 @@ __device__ unsigned long long g_bl[9];
 // reference's configuration (horizon 10, u_dim 5, nz = 8 + 24 = 32: N = 50) gets an instantiation in
 // which every loop bound and guard on N, nu, H and nz is a constant (the Cholesky's and the solves'
 // unrolled loops lose their per-column branches)
-template <int EPW, int HS = 0, int NUS = 0, int NZS = 0>
-__global__ __launch_bounds__(64 * EPW) void k_bilinear(BDev K, const double* __restrict__ A,
-                                                          const double* __restrict__ Bm,
-                                                          const double* __restrict__ Hh, int n,
-                                                          const double* __restrict__ z0g,
-                                                          const double* __restrict__ win,
-                                                          double* __restrict__ uprev, float* __restrict__ action) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
+//
+// BOX (k_bilinear_box, sim_koopman_bilinear_box_step): the same QP with the input limit in it, in the
+// model inputs w [N] (include/koopman_mpc.h):  min 1/2 w'P w - g'w,  lo <= w <= hi.  In w the state
+// term of both kinds is the 'mpc' form (X_k = M_k); 'delta_mpc' differs in the input term, r D'D (D the
+// block first difference: 2r on the diagonal blocks, r on the last one, -r beside them), and in the
+// right-hand side: no C_t u_prev in e_t, and r u_prev added on block 0.  The phases up to the packed
+// P = Pi Hess Pi' are shared; the Cholesky and the solves are replaced by projected Gauss-Seidel in
+// registers, one lane per row:
+//   lane i holds row i of P (both triangles, read once from the packed LDS copy), w_i, lo_i, hi_i,
+//   1 / P_ii and the running gradient r_i = (P w - g)_i;
+//   step i of a sweep: every lane forms clip(w - r / P_ii) - w, lane i's value is broadcast by
+//   readlane, lane i takes its clipped value, every lane does r += P[.][i] delta -- no dot product and
+//   no LDS traffic in the sweep, monotone descent, no tuning parameter.  The sweep runs over the lanes
+//   in order, i.e. over the time blocks from the last to the first (the reversed order Pi).
+//   Start: w = clip(0).  There is no factorisation in this kernel, so an env whose unconstrained
+//   minimiser lies inside the box is iterated like every other one: it gets iters > 0 and is solved to
+//   tol (the DKUC step returns such an env with iters = 0).
+//   Stop test, after EVERY sweep: res = w - clip(w - r / Lhat, lo, hi) from the maintained gradient,
+//   Lhat = ||P||_inf of this env (a lane's absolute row sum, then the wave maximum); done when
+//   ||res||_inf <= tol.  iters counts sweeps; at max_iter: ok = 0, iters = max_iter, the last iterate
+//   (every entry is a projection: inside the box).
+struct BXDev {
+  double umax, tol;
+  int max_iter;
+  double* plan;  // [H][nu][n] or null
+  int* ok;       // [n] or null
+  int* iters;    // [n] or null
+};
+constexpr int BBOX_MAX_ITER = 128;  // default (twice the measured maximum, rounded up)
+DEVI double clipd(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
+
+template <int EPW, int HS, int NUS, int NZS, bool BOX>
+DEVI void bilinear_body(double* lds, const BDev& K, const BXDev& bx, const double* __restrict__ A,
+                        const double* __restrict__ Bm, const double* __restrict__ Hh, int n,
+                        const double* __restrict__ z0g, const double* __restrict__ win,
+                        double* __restrict__ uprev, float* __restrict__ action) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // XCD-aware chunking: workgroups are dealt round-robin over the 8 XCDs, so chunk the envs per
   // XCD (workgroup b runs chunk (b % 8) G/8 + b / 8): neighbouring envs -- which share the cache
@@ -369,7 +398,7 @@ __global__ __launch_bounds__(64 * EPW) void k_bilinear(BDev K, const double* __r
           if (t < NTz && row < nz) {
             if (fc < nu && k < H) {
               M[o] = acc[t][r];
-              X[k * xs + o] = K.delta ? X[(k - 1) * xs + o] + acc[t][r] : acc[t][r];
+              X[k * xs + o] = (K.delta && !BOX) ? X[(k - 1) * xs + o] + acc[t][r] : acc[t][r];
             } else if (fc == nu) {
               Zs[k * nz + row] = acc[t][r];
             }
@@ -389,7 +418,7 @@ __global__ __launch_bounds__(64 * EPW) void k_bilinear(BDev K, const double* __r
       for (int s2 = 0; s2 < 16; s2++) wt = s2 == t ? wv[s2] : wt;
       if (t >= 16) wt = win[((size_t)t * nz + lane) * n + e];
       double ev = wt - Zs[(t + 1) * nz + lane];
-      if (K.delta) {
+      if (K.delta && !BOX) {
 #pragma unroll
         for (int c = 0; c < 8; c++)
           if (c < nu) ev = fma(-X[t * xs + lane * nu + c], up[c], ev);
@@ -480,11 +509,78 @@ __global__ __launch_bounds__(64 * EPW) void k_bilinear(BDev K, const double* __r
     for (int b = 0; b + d < H; b++) {
       const int a1 = (b + d) * nu + c1, a2 = b * nu + c2, o = a1 * (a1 + 1) / 2 + a2;
       S += G[o];
-      P[o] = fma(K.q, S, rd);
+      if constexpr (BOX) {  // 'delta_mpc': r D'D in the reversed order (block b = 0 is the last time block)
+        const double rb = !K.delta ? rd : c1 != c2 ? 0.0 : d == 0 ? (b == 0 ? K.r : 2.0 * K.r) : d == 1 ? -K.r : 0.0;
+        P[o] = fma(K.q, S, rb);
+      } else {
+        P[o] = fma(K.q, S, rd);
+      }
     }
   }
   wsync();
   BL_STAMP(5);
+  if constexpr (BOX) {
+    // the plan's own entry of lane a: time block ls, input lc (above); u_prev of that input
+    double upl = 0.0;
+#pragma unroll
+    for (int c = 0; c < 8; c++) upl = lc == c ? up[c] : upl;
+    const bool live = lane < N;
+    if (K.delta && live && ls == 0) rhs = fma(K.r, upl, rhs);
+    double lo = live ? -bx.umax : 0.0, hi = live ? bx.umax : 0.0;
+    if (!K.delta && live && ls == 0) lo -= upl, hi -= upl;  // |v_0 + u_prev| <= u_max: what is applied
+    // row `lane` of P, both triangles (lanes >= N and columns >= N: zero)
+    double prow[64];
+#pragma unroll
+    for (int k = 0; k < 64; k++) {
+      const int hi_i = max(lane, k), lo_i = min(lane, k);
+      prow[k] = (live && k < N) ? P[hi_i * (hi_i + 1) / 2 + lo_i] : 0.0;
+    }
+    const double idg = live ? 1.0 / P[lane * (lane + 1) / 2 + lane] : 0.0;
+    double lh = 0.0;
+#pragma unroll
+    for (int k = 0; k < 64; k++) lh += fabs(prow[k]);
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) lh = fmax(lh, __shfl_xor(lh, s));
+    const double ilh = 1.0 / lh;
+    // start: w = clip(0), gradient r = P w - g
+    double wl = clipd(0.0, lo, hi);
+    double gr = -rhs;
+#pragma unroll
+    for (int k = 0; k < 64; k++)
+      if (k < N) gr = fma(prow[k], rdlane(wl, k), gr);
+    int it = 0, done = 0;
+    while (it < bx.max_iter) {
+      it++;
+#pragma unroll
+      for (int i = 0; i < 64; i++)
+        if (i < N) {
+          const double wn = clipd(fma(-gr, idg, wl), lo, hi);
+          const double di = rdlane(wn - wl, i);
+          if (lane == i) wl = wn;
+          gr = fma(prow[i], di, gr);
+        }
+      double res = fabs(wl - clipd(fma(-gr, ilh, wl), lo, hi));
+#pragma unroll
+      for (int s = 1; s < 64; s <<= 1) res = fmax(res, __shfl_xor(res, s));
+      if (rdlane(res, 0) <= bx.tol) {
+        done = 1;
+        break;
+      }
+    }
+    if (live) {
+      if (bx.plan) bx.plan[((size_t)ls * nu + lc) * n + e] = wl;
+      if (ls == 0) {  // u0 = w_0 ('delta_mpc') or v_0 + u_prev (the sum may round one ulp past the limit)
+        const double u0 = K.delta ? wl : clipd(wl + upl, -bx.umax, bx.umax);
+        uprev[(size_t)lc * n + e] = u0;
+        action[(size_t)e * nu + lc] = (float)u0;
+      }
+    }
+    if (lane == 0) {
+      if (bx.ok) bx.ok[e] = done;
+      if (bx.iters) bx.iters[e] = it;
+    }
+    return;
+  }
   // Cholesky P = L L' with the rows in registers: lane i holds row i (compile-time column index,
   // N <= 64), in blocks of 4 columns.  Inside a block, column j is updated by the block's earlier
   // columns with L[j][q] taken by readlane (uniform), then scaled by its pivot; the trailing
@@ -571,6 +667,29 @@ __global__ __launch_bounds__(64 * EPW) void k_bilinear(BDev K, const double* __r
     action[(size_t)e * nu + c0] = (float)fmin(fmax(u0, -K.uclip), K.uclip);
   }
   BL_STAMP(8);
+}
+
+template <int EPW, int HS = 0, int NUS = 0, int NZS = 0>
+__global__ __launch_bounds__(64 * EPW) void k_bilinear(BDev K, const double* __restrict__ A,
+                                                          const double* __restrict__ Bm,
+                                                          const double* __restrict__ Hh, int n,
+                                                          const double* __restrict__ z0g,
+                                                          const double* __restrict__ win,
+                                                          double* __restrict__ uprev, float* __restrict__ action) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  bilinear_body<EPW, HS, NUS, NZS, false>(lds, K, BXDev{}, A, Bm, Hh, n, z0g, win, uprev, action);
+}
+
+template <int EPW, int HS = 0, int NUS = 0, int NZS = 0>
+__global__ __launch_bounds__(64 * EPW) void k_bilinear_box(BDev K, BXDev bx, const double* __restrict__ A,
+                                                              const double* __restrict__ Bm,
+                                                              const double* __restrict__ Hh, int n,
+                                                              const double* __restrict__ z0g,
+                                                              const double* __restrict__ win,
+                                                              double* __restrict__ uprev,
+                                                              float* __restrict__ action) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  bilinear_body<EPW, HS, NUS, NZS, true>(lds, K, bx, A, Bm, Hh, n, z0g, win, uprev, action);
 }
 
 // ---------------------------------------------------------------- open-loop prediction
@@ -734,6 +853,10 @@ struct sim_koopman {
   // DBKN (sim_koopman_set_bilinear): A [nz][nz], B [nz][nu], Hhat [j][(i nu + c)]
   BDev bd{};
   double *d_A = nullptr, *d_B = nullptr, *d_Hh = nullptr;
+  // the DBKN step with input limits (sim_koopman_set_bilinear_box; dropped by set_bilinear)
+  bool bbox = false;
+  double bb_umax = 0.0, bb_tol = 0.0;
+  int bb_max_iter = 0;
   // open-loop prediction (sim_koopman_set_model): [A | B] fragments, then the Hhat fragments
   PDev pd{};
   double* d_model = nullptr;
@@ -876,6 +999,7 @@ void sim_koopman_free(sim_koopman* k) {
 int sim_koopman_set_bilinear(sim_koopman* k, const double* A, const double* B, const double* Hhat, int delta,
                              double q, double r) {
   if (!k || !A || !B || !Hhat) return soarm_set_error(SIM_E_ARG, "null argument");
+  k->bbox = false;  // (the constrained step's options belong to the model they were set for)
   const int nz = k->kd.nz, nu = k->kd.ud, H = k->kd.H, N = H * nu;
   if (nz > 64 || nu > 8 || N > 64) return soarm_set_error(SIM_E_MODEL, "bilinear MPC: nz <= 64, u_dim <= 8, H * u_dim <= 64");
   if (!(q > 0.0) || !(r > 0.0)) return soarm_set_error(SIM_E_ARG, "bilinear MPC: q and r must be positive");
@@ -926,6 +1050,49 @@ int sim_koopman_bilinear_step(sim_koopman* k, int n, const double* z0, const dou
                      ((size_t)k->bd.per_env * ep + (size_t)k->bd.nz * (k->bd.nz + 1)) * sizeof(double), (hipStream_t)stream,
                      k->bd, k->d_A, k->d_B,
                      k->d_Hh, n, z0, window, u_prev, action);
+  KCHECK(hipGetLastError());
+  return SIM_OK;
+}
+
+// The DBKN step with input limits.  k_bilinear_box runs on k_bilinear's LDS plan (the sweep lives in
+// registers and needs no LDS of its own) and on fewer registers (no Cholesky rows beside P's), so
+// every shape set_bilinear accepts is accepted here: there is no SIM_E_MODEL of its own.
+int sim_koopman_set_bilinear_box(sim_koopman* k, const sim_koopman_box_opts* opts) {
+  if (!k) return soarm_set_error(SIM_E_ARG, "null argument");
+  k->bbox = false;  // a refusal below leaves bilinear_box_step refused and everything else as it was
+  if (!k->d_A) return soarm_set_error(SIM_E_ARG, "sim_koopman_set_bilinear was not called");
+  if (int rc = koopman_box_check_opts(opts)) return rc;
+  const double umax = opts ? opts->u_max : k->bd.uclip;
+  if (!(umax > 0.0)) return soarm_set_error(SIM_E_ARG, "box MPC: u_max must be positive");
+  KCHECK(hipSetDevice(k->device));
+  for (const void* f :
+       {(const void*)k_bilinear_box<8>, (const void*)k_bilinear_box<6>, (const void*)k_bilinear_box<4>,
+        (const void*)k_bilinear_box<2>, (const void*)k_bilinear_box<1>, (const void*)k_bilinear_box<8, 10, 5, 32>})
+    KCHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  k->bb_umax = umax, k->bb_tol = opts ? opts->tol : 1e-9, k->bb_max_iter = opts ? opts->max_iter : BBOX_MAX_ITER;
+  k->bbox = true;
+  return SIM_OK;
+}
+
+int sim_koopman_bilinear_box_step(sim_koopman* k, int n, const double* z0, const double* window, double* u_prev,
+                                  double* plan, float* action, int32_t* ok, int32_t* iters, void* stream) {
+  if (!k || !z0 || !window || !u_prev || !action || n < 0) return soarm_set_error(SIM_E_ARG, "bad argument");
+  if (!k->d_A || !k->bbox) return soarm_set_error(SIM_E_ARG, "sim_koopman_set_bilinear_box was not called (or refused)");
+  if (n == 0) return SIM_OK;
+  const int ep = k->bd.epw;
+  const bool ref_shape = k->bd.H == 10 && k->bd.nu == 5 && k->bd.nz == 32 && ep == 8;  // (static shapes)
+  auto kern = ref_shape ? k_bilinear_box<8, 10, 5, 32>
+              : ep == 8 ? k_bilinear_box<8>
+              : ep == 6 ? k_bilinear_box<6>
+              : ep == 4 ? k_bilinear_box<4>
+              : ep == 2 ? k_bilinear_box<2>
+                        : k_bilinear_box<1>;
+  BXDev bx{};
+  bx.umax = k->bb_umax, bx.tol = k->bb_tol, bx.max_iter = k->bb_max_iter;
+  bx.plan = plan, bx.ok = ok, bx.iters = iters;
+  hipLaunchKernelGGL(kern, dim3((n + ep - 1) / ep), dim3(64 * ep),
+                     ((size_t)k->bd.per_env * ep + (size_t)k->bd.nz * (k->bd.nz + 1)) * sizeof(double), (hipStream_t)stream,
+                     k->bd, bx, k->d_A, k->d_B, k->d_Hh, n, z0, window, u_prev, action);
   KCHECK(hipGetLastError());
   return SIM_OK;
 }
