@@ -154,7 +154,7 @@ int sim_koopman_box_step(sim_koopman* k, int n, const float* x, const double* z0
                          double* u_prev, double* plan, int warm, float* action, int32_t* ok, int32_t* iters,
                          void* stream);
 
-/* The DBKN control step with input limits (csrc/koopman_mpc.hip, k_bilinear_box): the problem of
+/* The DBKN control step with input limits (csrc/koopman_bilinear.hip, k_bilinear_box): the problem of
    sim_koopman_box_step above -- the same kinds, bounds and u0 -- with B_total = B + sum_j z0_j Hhat_j
    in place of B, so P = P_e differs per env and frame and nothing of it can be prepared on the host.
    One wave per env builds P_e as sim_koopman_bilinear_step builds its Hessian and solves the box QP by

@@ -14,13 +14,14 @@ import time
 from .abi import LIB_PATH, PKG_DIR
 
 SRC_DIR = os.path.join(PKG_DIR, "csrc")
-SOURCES = ["soarm_sim.hip", "soarm_cforce.hip", "koopman_mpc.hip", "koopman_box.hip", "koopman_train.hip", "soarm_cpu.hip",
-           "soarm_model.hip"]
+SOURCES = ["soarm_sim.hip", "soarm_cforce.hip", "koopman_mpc.hip", "koopman_bilinear.hip", "koopman_predict.hip",
+           "koopman_box.hip", "koopman_train.hip", "soarm_cpu.hip", "soarm_model.hip"]
 # translation units compiled for the host only (the CPU backend, the model build: no kernels)
 HOST_ONLY = {"soarm_cpu.hip", "soarm_model.hip"}
 HEADERS = ["dmodel.h", "soarm_kernels.h", "soarm_step.h", "soarm_collide.h", "soarm_pgs.h", "soarm_rs.h", "soarm_newton.h",
            "soarm_prof.h", "soarm_substep.h",
-           "soarm_env.h", "soarm_ikbox.h", "sim_internal.h", "koopman_frag.h", "koopman_train_plan.h"]
+           "soarm_env.h", "soarm_ikbox.h", "sim_internal.h", "koopman_frag.h", "koopman_layout.h", "koopman_internal.h",
+           "koopman_train_plan.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize: the per-lane algebra gains nothing from v_pk_* packing; the
 # packing's operand shuffles (v_mov) and the extra register pressure (AGPR

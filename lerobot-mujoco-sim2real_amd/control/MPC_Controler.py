@@ -15,14 +15,14 @@ computed once on the host in float64) and every per-env evaluation runs in the H
   ``koopman_box.hip``; ``control/koopman.box_plan`` is the same iteration in numpy)
 * :meth:`set_box_bilinear` / :meth:`step_box_bilinear` — the same for a DBKN net, whose Hessian
   differs per env and frame: projected Gauss-Seidel per env (``sim_koopman_bilinear_box_step``,
-  ``koopman_mpc.hip`` ``k_bilinear_box``; ``control/koopman.box_plan_bilinear`` in numpy)
+  ``koopman_bilinear.hip`` ``k_bilinear_box``; ``control/koopman.box_plan_bilinear`` in numpy)
 * :meth:`predict` / :meth:`evaluate` — the model's open-loop prediction of a device rollout and the
   reference's evaluation metrics (``train.py:35-87``), all steps in one launch (``sim_koopman_predict``)
 
 A bilinear DBKN model (``net.H``, ``KoopmanBase.py:62-110``) linearises its input matrix at each
 frame's lifted state (``linearize_B``, ``:46-63``), so the QP differs per env and frame:
 :meth:`step_bilinear` lifts the state in the HIP library and solves the n QPs in float64 on the
-device, one wave per env (``sim_koopman_bilinear_step``, ``koopman_mpc.hip`` ``k_bilinear``;
+device, one wave per env (``sim_koopman_bilinear_step``, ``koopman_bilinear.hip`` ``k_bilinear``;
 ``control/koopman.bilinear_first_move`` is the same algebra in torch, kept as its CPU cross-check).
 
 There is no CPU path: without the library or a GPU, construction raises.
@@ -92,7 +92,7 @@ class MPCController:
         self._Ah = np.ascontiguousarray(self.Ad, np.float64)
         self._Bh = np.ascontiguousarray(self.Bd, np.float64)
         self._Hh = np.ascontiguousarray(np.stack(self.H_hat_list), np.float64) if self.bilinear else None  # [j][nz][nu]
-        # the open-loop prediction kernel (koopman_mpc.hip k_predict).  A model that only this kernel's
+        # the open-loop prediction kernel (koopman_predict.hip k_predict).  A model that only this kernel's
         # LDS plan refuses (SIM_E_MODEL) still controls: predict() raises with the library's message
         rc = self.lib.sim_koopman_set_model(self._h, self._Ah.ctypes.data_as(C.c_void_p),
                                             self._Bh.ctypes.data_as(C.c_void_p),
@@ -100,7 +100,7 @@ class MPCController:
         self._predict_refused = self.lib.sim_last_error().decode() if rc == abi.E_MODEL else None
         if rc != abi.E_MODEL:
             abi.check(self.lib, rc)
-        if self.bilinear:  # the per-env QP kernel (koopman_mpc.hip k_bilinear)
+        if self.bilinear:  # the per-env QP kernel (koopman_bilinear.hip k_bilinear)
             abi.check(self.lib, self.lib.sim_koopman_set_bilinear(
                 self._h, self._Ah.ctypes.data_as(C.c_void_p), self._Bh.ctypes.data_as(C.c_void_p),
                 self._Hh.ctypes.data_as(C.c_void_p), int(self.MPC_type == "delta_mpc"), Q_WEIGHT, R_WEIGHT))
@@ -119,6 +119,26 @@ class MPCController:
     def _f32(self, x, cols):
         t = self.torch.as_tensor(x, dtype=self.torch.float32, device=self.device)
         return t.reshape(-1, cols).contiguous()
+
+    def _check(self, who, want):
+        """The step kernels read raw pointers: every tensor of want = {name: (tensor, dtype, shape)} must be
+        contiguous, of that dtype and shape, on this controller's device -- anything else is refused here."""
+        dev = self.device
+        for name, (t, dt, shape) in want.items():
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device.type != "cuda" or \
+                    (dev.index is not None and t.device.index != dev.index):
+                raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor of shape {shape} on {dev}; "
+                                 f"got {t.dtype} {tuple(t.shape)} on {t.device} (contiguous: {t.is_contiguous()})")
+
+    def _outputs(self, n, action, flags=False):
+        """action [n, u_dim] float32 (the caller's, or new) and, with flags, ok [n] and iters [n] int32."""
+        torch = self.torch
+        if action is None:
+            action = torch.empty((n, self.u_dim), dtype=torch.float32, device=self.device)
+        if not flags:
+            return action
+        return (action, torch.empty((n,), dtype=torch.int32, device=self.device),
+                torch.empty((n,), dtype=torch.int32, device=self.device))
 
     # ------------------------------------------------------------- batched device API
     def encode(self, x):
@@ -149,8 +169,7 @@ class MPCController:
         u_prev <- u0; returns action = clip(u0) [n, u_dim] float32 (device)."""
         n = u_prev.shape[1]
         xx = None if x is None else self._f32(x, self.in_dim)
-        if action is None:
-            action = self.torch.empty((n, self.u_dim), dtype=self.torch.float32, device=self.device)
+        action = self._outputs(n, action)
         abi.check(self.lib, self.lib.sim_koopman_mpc_step(self._h, n, _ptr(xx), _ptr(z0), _ptr(ff), _ptr(u_prev),
                                                           _ptr(action), self._stream()))
         return action
@@ -165,21 +184,14 @@ class MPCController:
         if z0 is None:
             z0 = self.encode(x)
         n = u_prev.shape[1]
-        if action is None:
-            action = torch.empty((n, self.u_dim), dtype=torch.float32, device=self.device)
+        action = self._outputs(n, action)
         z0 = z0.contiguous()
         window = window.contiguous()
-        # k_bilinear reads raw pointers: float64 z0 [nz, n], a window of exactly H rows [H, nz, n]
-        # (short tails are zero-padded by the caller, lifted_window), float64 u_prev [u_dim, n] and a
-        # float32 action [n, u_dim], all contiguous on this device -- anything else is refused here
-        dev = torch.device(self.device) if not isinstance(self.device, torch.device) else self.device
-        want = {"z0": (z0, torch.float64, (self.Nkoopman, n)), "window": (window, torch.float64, (self.H, self.Nkoopman, n)),
-                "u_prev": (u_prev, torch.float64, (self.u_dim, n)), "action": (action, torch.float32, (n, self.u_dim))}
-        for name, (t, dt, shape) in want.items():
-            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device.type != "cuda" or \
-                    (dev.index is not None and t.device.index != dev.index):
-                raise ValueError(f"step_bilinear: {name} must be a contiguous {dt} tensor of shape {shape} on {dev}; "
-                                 f"got {t.dtype} {tuple(t.shape)} on {t.device} (contiguous: {t.is_contiguous()})")
+        # k_bilinear reads float64 z0 [nz, n], a window of exactly H rows [H, nz, n] (short tails are
+        # zero-padded by the caller, lifted_window), float64 u_prev [u_dim, n] and a float32 action [n, u_dim]
+        self._check("step_bilinear", {
+            "z0": (z0, torch.float64, (self.Nkoopman, n)), "window": (window, torch.float64, (self.H, self.Nkoopman, n)),
+            "u_prev": (u_prev, torch.float64, (self.u_dim, n)), "action": (action, torch.float32, (n, self.u_dim))})
         abi.check(self.lib, self.lib.sim_koopman_bilinear_step(self._h, n, _ptr(z0), _ptr(window), _ptr(u_prev),
                                                                _ptr(action), self._stream()))
         return action
@@ -214,20 +226,14 @@ class MPCController:
             self.set_box()
         n = u_prev.shape[1]
         xx = None if x is None else self._f32(x, self.in_dim)
-        if action is None:
-            action = torch.empty((n, self.u_dim), dtype=torch.float32, device=self.device)
-        ok = torch.empty((n,), dtype=torch.int32, device=self.device)
-        iters = torch.empty((n,), dtype=torch.int32, device=self.device)
+        action, ok, iters = self._outputs(n, action, flags=True)
         want = {"window": (window, torch.float64, (self.H, self.Nkoopman, n)),
                 "u_prev": (u_prev, torch.float64, (self.u_dim, n)), "action": (action, torch.float32, (n, self.u_dim))}
         if z0 is not None:
             want["z0"] = (z0, torch.float64, (self.Nkoopman, n))
         if plan is not None:
             want["plan"] = (plan, torch.float64, (self.H, self.u_dim, n))
-        for name, (t, dt, shape) in want.items():
-            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device.type != "cuda":
-                raise ValueError(f"step_box: {name} must be a contiguous {dt} tensor of shape {shape} on {self.device}; "
-                                 f"got {t.dtype} {tuple(t.shape)} on {t.device} (contiguous: {t.is_contiguous()})")
+        self._check("step_box", want)
         if xx is not None and xx.shape[0] != n:
             raise ValueError(f"step_box: x must hold {n} states; got {xx.shape[0]}")
         abi.check(self.lib, self.lib.sim_koopman_box_step(self._h, n, _ptr(xx), _ptr(z0), _ptr(window), _ptr(u_prev),
@@ -264,22 +270,14 @@ class MPCController:
         if z0 is None:
             z0 = self.encode(x)
         n = u_prev.shape[1]
-        if action is None:
-            action = torch.empty((n, self.u_dim), dtype=torch.float32, device=self.device)
+        action, ok, iters = self._outputs(n, action, flags=True)
         z0 = z0.contiguous()
         window = window.contiguous()
-        ok = torch.empty((n,), dtype=torch.int32, device=self.device)
-        iters = torch.empty((n,), dtype=torch.int32, device=self.device)
-        dev = self.device
         want = {"z0": (z0, torch.float64, (self.Nkoopman, n)), "window": (window, torch.float64, (self.H, self.Nkoopman, n)),
                 "u_prev": (u_prev, torch.float64, (self.u_dim, n)), "action": (action, torch.float32, (n, self.u_dim))}
         if plan is not None:
             want["plan"] = (plan, torch.float64, (self.H, self.u_dim, n))
-        for name, (t, dt, shape) in want.items():
-            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device.type != "cuda" or \
-                    (dev.index is not None and t.device.index != dev.index):
-                raise ValueError(f"step_box_bilinear: {name} must be a contiguous {dt} tensor of shape {shape} on {dev}; "
-                                 f"got {t.dtype} {tuple(t.shape)} on {t.device} (contiguous: {t.is_contiguous()})")
+        self._check("step_box_bilinear", want)
         abi.check(self.lib, self.lib.sim_koopman_bilinear_box_step(self._h, n, _ptr(z0), _ptr(window), _ptr(u_prev),
                                                                    _ptr(plan), _ptr(action), _ptr(ok), _ptr(iters),
                                                                    self._stream()))

@@ -126,7 +126,7 @@ def open_loop_prediction(net, x, u, relift=True):
     reference's ``pred_and_eval_loss_old`` (``models/losses.py:132-173``, what ``evaluate()``
     runs, ``train.py:35-87``); ``relift=False`` its ``pred_and_eval_loss_new`` (``:175-215``).
     Returns pred [N, T+1, x_dim].  The literal loop: the cross-check of
-    ``MPCController.predict`` (``koopman_mpc.hip`` ``k_predict``), which runs it in one launch."""
+    ``MPCController.predict`` (``koopman_predict.hip`` ``k_predict``), which runs it in one launch."""
     if net.lA.weight.dtype != torch.float64:
         raise ValueError("open_loop_prediction runs in float64: call net.double() first (Koopman_MPC.py:263)")
     with torch.no_grad():
@@ -245,6 +245,38 @@ def bilinear_first_move(A, B, Hhat, z0, window, u_prev, kind, H, q=50.0, r=0.5):
     return v[:, :nu].T + u_prev
 
 
+def _powers(A, H):
+    """[I, A, A^2, ..., A^H]."""
+    P = [np.eye(A.shape[0])]
+    for _ in range(H):
+        P.append(A @ P[-1])
+    return P
+
+
+def _prediction(A, B, H):
+    """The stacked prediction Z = Phi z0 + Gam U over t = 0..H-1: (A's powers [I .. A^H],
+    Phi = [A; A^2; ...; A^H], Gam[t, s] = A^(t-s) B for s <= t)."""
+    nz, nu = B.shape
+    P = _powers(A, H)
+    Phi = np.vstack(P[1:])
+    Gam = np.zeros((H * nz, H * nu))
+    for t in range(H):
+        for s in range(t + 1):
+            Gam[t * nz:(t + 1) * nz, s * nu:(s + 1) * nu] = P[t - s] @ B
+    return P, Phi, Gam
+
+
+def _move_penalty(kind, H, nu):
+    """The input term's matrix of the constrained steps, in the model inputs w: D'D ('delta_mpc': D the
+    block first difference) or I ('mpc')."""
+    if kind == "delta_mpc":
+        D = np.kron(np.eye(H) - np.eye(H, k=-1), np.eye(nu))
+        return D.T @ D
+    if kind == "mpc":
+        return np.eye(H * nu)
+    raise ValueError(f"MPC_type {kind!r}: 'mpc' or 'delta_mpc'")
+
+
 def condensed_gains(A, B, H, kind, q=50.0, r=0.5):
     """Closed-form first move of the unconstrained MPC QP (MPC_Controler.py:65-141, state_full).
 
@@ -256,14 +288,7 @@ def condensed_gains(A, B, H, kind, q=50.0, r=0.5):
     Gz [nu, nz], Gu [nu, nu]) with u0 = Gr Rbar + Gz z0 + Gu u_prev."""
     A, B = np.asarray(A, np.float64), np.asarray(B, np.float64)
     nz, nu = B.shape
-    P = [np.eye(nz)]
-    for _ in range(H):
-        P.append(A @ P[-1])
-    Phi = np.vstack(P[1:])
-    Gam = np.zeros((H * nz, H * nu))
-    for t in range(H):
-        for s in range(t + 1):
-            Gam[t * nz:(t + 1) * nz, s * nu:(s + 1) * nu] = P[t - s] @ B
+    _, Phi, Gam = _prediction(A, B, H)
     if kind == "delta_mpc":
         S = np.kron(np.tril(np.ones((H, H))), np.eye(nu))
         Gd = Gam @ S
@@ -304,23 +329,11 @@ def box_problem(A, B, H, kind, q=50.0, r=0.5):
     A, B = np.asarray(A, np.float64), np.asarray(B, np.float64)
     nz, nu = B.shape
     N = H * nu
-    Pw = [np.eye(nz)]
-    for _ in range(H):
-        Pw.append(A @ Pw[-1])
-    Phi = np.vstack(Pw[1:])
-    Gam = np.zeros((H * nz, N))
-    for t in range(H):
-        for s in range(t + 1):
-            Gam[t * nz:(t + 1) * nz, s * nu:(s + 1) * nu] = Pw[t - s] @ B
+    _, Phi, Gam = _prediction(A, B, H)
+    Rm = _move_penalty(kind, H, nu)
     Gu = np.zeros((N, nu))
     if kind == "delta_mpc":
-        D = np.kron(np.eye(H) - np.eye(H, k=-1), np.eye(nu))
-        Rm = D.T @ D
         Gu[:nu] = 2.0 * r * np.eye(nu)
-    elif kind == "mpc":
-        Rm = np.eye(N)
-    else:
-        raise ValueError(f"MPC_type {kind!r}: 'mpc' or 'delta_mpc'")
     P = 2.0 * (q * Gam.T @ Gam + r * Rm)
     P = 0.5 * (P + P.T)
     Gw = 2.0 * q * Gam.T
@@ -416,7 +429,7 @@ def box_plan(prob, z0, window, u_prev, u_max=0.5, tol=1e-9, max_iter=256, plan=N
 # ------------------------------------------------------------------ input-constrained MPC (DBKN)
 def box_plan_bilinear(A, B, Hhat, z0, window, u_prev, kind, H, u_max=0.5, tol=1e-9, max_iter=128, q=50.0, r=0.5):
     """The constrained DBKN control step in float64 numpy: what ``sim_koopman_bilinear_box_step``
-    computes (``koopman_mpc.hip`` ``k_bilinear_box``), by the same iteration, for n envs.  A [nz, nz],
+    computes (``koopman_bilinear.hip`` ``k_bilinear_box``), by the same iteration, for n envs.  A [nz, nz],
     B [nz, nu], Hhat [nz(j), nz, nu], z0 [n, nz], window [n, H, nz] (lifted reference rows, zero past the
     end), u_prev [n, nu].  Returns (w [n, N] the model inputs in natural order, u0 [n, nu], ok [n] int32,
     iters [n] int32).
@@ -442,9 +455,7 @@ def box_plan_bilinear(A, B, Hhat, z0, window, u_prev, kind, H, u_max=0.5, tol=1e
     u_prev = np.atleast_2d(np.asarray(u_prev, np.float64)).reshape(n, nu)
     rbar = np.asarray(window, np.float64).reshape(n, H, nz)
     Bt = B[None] + np.einsum("nj,jik->nik", z0, Hhat)                      # [n, nz, nu]
-    Pw = [np.eye(nz)]
-    for _ in range(H):
-        Pw.append(A @ Pw[-1])
+    Pw = _powers(A, H)
     Mk = np.stack([Pw[k] @ Bt for k in range(H)], 1)                        # A^k B_total [n, H, nz, nu]
     Gam = np.zeros((n, H, nz, H, nu))
     for t in range(H):
@@ -453,12 +464,9 @@ def box_plan_bilinear(A, B, Hhat, z0, window, u_prev, kind, H, u_max=0.5, tol=1e
     Gam = Gam.reshape(n, H * nz, N)
     e = rbar - np.stack([z0 @ Pw[t + 1].T for t in range(H)], 1)            # ref_t - A^(t+1) z0
     g = q * np.einsum("nka,nk->na", Gam, e.reshape(n, H * nz))
+    Rm = _move_penalty(kind, H, nu)
     if kind == "delta_mpc":
-        D = np.kron(np.eye(H) - np.eye(H, k=-1), np.eye(nu))
-        Rm = D.T @ D
         g[:, :nu] += r * u_prev
-    else:
-        Rm = np.eye(N)
     P = q * np.einsum("nka,nkb->nab", Gam, Gam) + r * Rm[None]
     P = 0.5 * (P + P.transpose(0, 2, 1))
     lo = np.full((n, N), -float(u_max))

@@ -36,12 +36,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/koopman_mpc.h"
-#include "koopman_frag.h"
-
-int soarm_set_error(int code, const std::string& msg);  // soarm_model.hip (sim_last_error)
-// koopman_mpc.hip: the handle's device, KDev, encoder fragments and the slot this unit's state hangs on
-void koopman_handle_view(sim_koopman* k, int* device, const void** kdev, const double** frag, void*** box);
+#include "koopman_internal.h"
 
 namespace {
 
@@ -69,7 +64,6 @@ DEVI void bounds(const XDev& X, int T, int r, int kq, const double up[2], double
   const double sh = (!X.delta && T == 0 && r < 2) ? up[r] : 0.0;
   lo = -m - sh, hi = m - sh;
 }
-DEVI double clipd(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
 
 // out = F v for the [NT][4 NT][64] fragments F (in LDS, + lane); k-steps outer, tiles inner
 DEVI void matvec(const double* F, int NT, const d4 (&v)[4], d4 (&out)[4]) {
@@ -118,37 +112,12 @@ __global__ __launch_bounds__(256) void k_box_step(KDev K, XDev X, const double* 
   __syncthreads();
   if (!z0) stage(lds, frag, K.total);  // (uniform: the encoder's fragments)
   const int lane = threadIdx.x & 63, kq = lane >> 4;
-  const int e = blockIdx.x * 64 + (threadIdx.x >> 6) * 16 + (lane & 15);
+  const int e = lane_env(lane);
   const bool live = e < n;  // tail lanes run on zero inputs (interior) and never load or store
-  double up[2];
-#pragma unroll
-  for (int s = 0; s < 2; s++) {
-    const int row = 4 * s + kq;
-    up[s] = (live && row < K.ud) ? uprev[(size_t)row * n + e] : 0.0;
-  }
-  double xb[2];
+  double up[2], xb[2];
   d4 act[KT];
-  if (z0) {
-#pragma unroll
-    for (int s = 0; s < 2; s++) {
-      const int row = 4 * s + kq;
-      xb[s] = (live && row < K.xd) ? z0[(size_t)row * n + e] : 0.0;
-    }
-#pragma unroll
-    for (int T = 0; T < KT; T++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int row = 16 * T + kq + 4 * r;
-        act[T][r] = (live && T < NTL && row < K.outw) ? z0[(size_t)(K.xd + row) * n + e] : 0.0;
-      }
-  } else {
-#pragma unroll
-    for (int s = 0; s < 2; s++) {
-      const int row = 4 * s + kq;
-      xb[s] = (live && row < K.xd) ? (double)x[(size_t)e * K.xd + row] : 0.0;
-    }
-    encode<NTL>(K, lds, lane, xb, act);
-  }
+  load_uprev(K, uprev, n, e, live, kq, up);
+  load_lifted<NTL>(K, lds, lane, n, e, live, x, z0, xb, act);
   // wu = K [window; z0; u_prev]: NT output tiles, the A fragments from global memory
   const int NT = X.NT, kst = X.kst;
   d4 wu[4];
@@ -280,11 +249,15 @@ typedef void (*BoxFn)(KDev, XDev, const double*, const double*, int, const float
                       double*, double*, int, float*, int32_t*, int32_t*);
 const BoxFn BOXSTEP[4] = {k_box_step<1>, k_box_step<2>, k_box_step<3>, k_box_step<4>};
 
-struct KBox {
+}  // namespace
+
+struct KBox {  // a handle's state of this unit (sim_koopman::box)
   int device = 0;
   XDev xd{};
   double* d = nullptr;  // [K | P | Mrho] fragments
 };
+
+namespace {
 
 // ---- host linear algebra (row-major, N <= 64)
 typedef std::vector<double> Mat;
@@ -373,19 +346,12 @@ int check_shape(int nz, int nu, int H) {
   return SIM_OK;
 }
 
-#define KCHECK(x)                                                                                  \
-  do {                                                                                             \
-    hipError_t e_ = (x);                                                                           \
-    if (e_ != hipSuccess) return soarm_set_error(SIM_E_HIP, std::string(#x ": ") + hipGetErrorString(e_)); \
-  } while (0)
-
 }  // namespace
 
-// the option checks, for sim_koopman_set_bilinear_box (koopman_mpc.hip): one helper serves both steps
+// the option checks, for sim_koopman_set_bilinear_box (koopman_bilinear.hip): one helper serves both steps
 int koopman_box_check_opts(const sim_koopman_box_opts* opts) { return check_opts(opts); }
 
-void koopman_box_release(void* box) {
-  KBox* b = static_cast<KBox*>(box);
+void koopman_box_release(KBox* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   (void)hipFree(b->d);
@@ -405,23 +371,19 @@ int sim_koopman_box_check(const sim_koopman_desc* d, const sim_koopman_box_opts*
 int sim_koopman_set_box(sim_koopman* k, const double* A, const double* B, int delta, double q, double r,
                         const sim_koopman_box_opts* opts) {
   if (!k || !A || !B) return soarm_set_error(SIM_E_ARG, "null argument");
-  int device;
-  const void* kdv;
-  const double* frag;
-  void** slot;
-  koopman_handle_view(k, &device, &kdv, &frag, &slot);
-  const KDev& K = *static_cast<const KDev*>(kdv);
+  const KDev& K = k->kd;
+  const klayout::Encoder enc = koopman_layout_of(K);
   // a refusal below leaves box_step refused and everything else as it was
-  koopman_box_release(*slot);
-  *slot = nullptr;
+  koopman_box_release(k->box);
+  k->box = nullptr;
   if (int rc = check_opts(opts)) return rc;
   if (!(q > 0.0) || !(r > 0.0)) return soarm_set_error(SIM_E_ARG, "box MPC: q and r must be positive");
-  const int nz = K.nz, nu = K.ud, H = K.H, N = H * nu, xd = K.xd, ntl = K.ntile[K.nl - 1];
+  const int nz = K.nz, nu = K.ud, H = K.H, N = H * nu, ntl = enc.ntl;
   if (int rc = check_shape(nz, nu, H)) return rc;
   XDev X{};
   X.N = N, X.NT = (N + 15) / 16, X.delta = delta ? 1 : 0;
   X.ksw = (H * nz + 3) / 4;
-  X.kst = X.ksw + 2 + 4 * ntl + 2;
+  X.kst = X.ksw + klayout::ks_zu(enc);
   X.kcount = X.NT * X.kst * 64;
   X.pm = X.NT * 4 * X.NT * 64;
   X.umax = opts ? opts->u_max : K.uclip;
@@ -431,7 +393,7 @@ int sim_koopman_set_box(sim_koopman* k, const double* A, const double* B, int de
   if (!(X.umax > 0.0)) return soarm_set_error(SIM_E_ARG, "box MPC: u_max must be positive");
   X.vote = std::max(K.total, 2 * X.pm);
   const size_t lds_bytes = (size_t)(X.vote + 2) * sizeof(double);  // (+ the vote word)
-  if (lds_bytes > 160 * 1024)
+  if (lds_bytes > KOOPMAN_LDS_BYTES)
     return soarm_set_error(SIM_E_MODEL, "box MPC: the LDS plan (" + std::to_string(lds_bytes) + " bytes) must be <= 160 KiB");
 
   // Gam[t][s] = A^(t-s) B, Phi = [A; A^2; ..; A^H]
@@ -492,33 +454,18 @@ int sim_koopman_set_box(sim_koopman* k, const double* A, const double* B, int de
 
   // fragments: K's k order is [window (H nz, flat) | x rows 0..7 | feature rows (16 per tile) | u_prev 0..7]
   std::vector<double> blob((size_t)X.kcount + 2 * X.pm, 0.0);
-  auto kcol = [&](int s, int kq) -> int {
-    if (s < X.ksw) return 4 * s + kq < hz ? 4 * s + kq : -1;
-    int kk = 4 * (s - X.ksw) + kq;
-    if (kk < 8) return kk < xd ? hz + kk : -1;
-    kk -= 8;
-    if (kk < 16 * ntl) return kk < K.outw ? hz + xd + kk : -1;
-    kk -= 16 * ntl;
-    return kk < nu ? hz + nz + kk : -1;
-  };
-  for (int T = 0; T < X.NT; T++)
-    for (int s = 0; s < X.kst; s++)
-      for (int lane = 0; lane < 64; lane++) {
-        const int row = 16 * T + (lane & 15), c = kcol(s, lane >> 4);
-        blob[((size_t)T * X.kst + s) * 64 + lane] = (row < N && c >= 0) ? Kall[(size_t)row * kc + c] : 0.0;
-      }
-  for (int T = 0; T < X.NT; T++)
-    for (int s = 0; s < 4 * X.NT; s++)
-      for (int lane = 0; lane < 64; lane++) {
-        const int row = 16 * T + (lane & 15), c = 4 * s + (lane >> 4);
-        const size_t o = ((size_t)T * 4 * X.NT + s) * 64 + lane;
-        const bool in = row < N && c < N;
-        blob[X.kcount + o] = in ? P[(size_t)row * N + c] : 0.0;
-        blob[(size_t)X.kcount + X.pm + o] = in ? Mr[(size_t)row * N + c] : 0.0;
-      }
-  KCHECK(hipSetDevice(device));
+  klayout::fill_frag(blob.data(), X.NT, X.kst, [&](int row, int kk) {
+    const int c = kk < 4 * X.ksw ? (kk < hz ? kk : -1) : klayout::zu_col(enc, kk - 4 * X.ksw, hz);
+    return (row < N && c >= 0) ? Kall[(size_t)row * kc + c] : 0.0;
+  });
+  klayout::each_frag(X.NT, 4 * X.NT, [&](int pos, int row, int c) {
+    const bool in = row < N && c < N;
+    blob[(size_t)X.kcount + pos] = in ? P[(size_t)row * N + c] : 0.0;
+    blob[(size_t)X.kcount + X.pm + pos] = in ? Mr[(size_t)row * N + c] : 0.0;
+  });
+  KCHECK(hipSetDevice(k->device));
   KBox* b = new KBox;
-  b->device = device, b->xd = X;
+  b->device = k->device, b->xd = X;
   if (hipMalloc(&b->d, blob.size() * sizeof(double)) != hipSuccess) {
     delete b;
     return soarm_set_error(SIM_E_HIP, "hipMalloc failed");
@@ -526,12 +473,12 @@ int sim_koopman_set_box(sim_koopman* k, const double* A, const double* B, int de
   // the state is published only once the upload and the kernel's LDS attribute are in place
   hipError_t he = hipMemcpy(b->d, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice);
   if (he == hipSuccess)
-    he = hipFuncSetAttribute((const void*)BOXSTEP[ntl - 1], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    he = koopman_raise_lds((const void*)BOXSTEP[ntl - 1]);
   if (he != hipSuccess) {
     koopman_box_release(b);
     return soarm_set_error(SIM_E_HIP, std::string("box MPC: upload failed: ") + hipGetErrorString(he));
   }
-  *slot = b;
+  k->box = b;
   return SIM_OK;
 }
 
@@ -539,17 +486,12 @@ int sim_koopman_box_step(sim_koopman* k, int n, const float* x, const double* z0
                          double* u_prev, double* plan, int warm, float* action, int32_t* ok, int32_t* iters,
                          void* stream) {
   if (!k || !window || !u_prev || !action || (!x && !z0) || n < 0) return soarm_set_error(SIM_E_ARG, "bad argument");
-  int device;
-  const void* kdv;
-  const double* frag;
-  void** slot;
-  koopman_handle_view(k, &device, &kdv, &frag, &slot);
-  const KBox* b = static_cast<const KBox*>(*slot);
+  const KBox* b = k->box;
   if (!b) return soarm_set_error(SIM_E_ARG, "sim_koopman_set_box was not called (or refused the model)");
   if (n == 0) return SIM_OK;
-  const KDev& K = *static_cast<const KDev*>(kdv);
+  const KDev& K = k->kd;
   hipLaunchKernelGGL(BOXSTEP[K.ntile[K.nl - 1] - 1], dim3((n + 63) / 64), dim3(256),
-                     (size_t)(b->xd.vote + 2) * sizeof(double), (hipStream_t)stream, K, b->xd, frag, b->d,
+                     (size_t)(b->xd.vote + 2) * sizeof(double), (hipStream_t)stream, K, b->xd, k->d_frag, b->d,
                      n, x, z0, window, u_prev, plan, warm, action, ok, iters);
   KCHECK(hipGetLastError());
   return SIM_OK;

@@ -1,6 +1,7 @@
-// koopman_frag.h — the f64-MFMA fragment helpers shared by koopman_mpc.hip (control, prediction)
-// and koopman_train.hip (training): the device-side layout of an encoder's fragment blob, the
-// MFMA wrapper, LDS staging and the register-chained encoder.
+// koopman_frag.h — the f64-MFMA device helpers shared by the Koopman units (koopman_mpc.hip,
+// koopman_bilinear.hip, koopman_predict.hip, koopman_box.hip, koopman_train.hip): the device-side
+// layout of an encoder's fragment blob, the MFMA wrapper, LDS staging, the register-chained encoder
+// and the loads of a control step's operands.  The host-side layout is koopman_layout.h's.
 //
 // Layouts (v_mfma_f64_16x16x4_f64, one wave, samples on the N side):
 //   A operand  lane l holds A[row l & 15][k l >> 4] of the k-step;
@@ -118,6 +119,47 @@ DEVI void load_pair(const float* __restrict__ p, bool ok, int dim, int kq, doubl
   for (int s = 0; s < 2; s++) {
     const int row = 4 * s + kq;
     out[s] = (ok && row < dim) ? (double)p[row] : 0.0;
+  }
+}
+
+DEVI double clipd(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
+
+// ---- the kernels of 4 waves x 16 envs (k_encode, k_mpc_step, k_feedforward, k_box_step)
+// this lane's env: column lane & 15 of its wave's 16
+DEVI int lane_env(int lane) { return blockIdx.x * 64 + (threadIdx.x >> 6) * 16 + (lane & 15); }
+
+// rows 4 s + kq of u_prev [ud][n] as the B operands of the last two k-steps
+DEVI void load_uprev(const KDev& K, const double* __restrict__ uprev, int n, int e, bool live, int kq, double up[2]) {
+#pragma unroll
+  for (int s = 0; s < 2; s++) {
+    const int row = 4 * s + kq;
+    up[s] = (live && row < K.ud) ? uprev[(size_t)row * n + e] : 0.0;
+  }
+}
+
+// the lifted state of this lane's env as B operands, xb (the x rows) and act (the feature tiles): z0 [nz][n]
+// where it is given (get_control(p), MPC_Controler.py:143), else Psi_o(x) by the encoder (x [n][xd] f32,
+// widened as torch.DoubleTensor(obs); the encoder's fragments staged in lds)
+template <int NTL>
+DEVI void load_lifted(const KDev& K, const double* lds, int lane, int n, int e, bool live,
+                      const float* __restrict__ x, const double* __restrict__ z0, double xb[2], d4 (&act)[KT]) {
+  const int kq = lane >> 4;
+  if (z0) {
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+      const int row = 4 * s + kq;
+      xb[s] = (live && row < K.xd) ? z0[(size_t)row * n + e] : 0.0;
+    }
+#pragma unroll
+    for (int T = 0; T < KT; T++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int row = 16 * T + kq + 4 * r;
+        act[T][r] = (live && T < NTL && row < K.outw) ? z0[(size_t)(K.xd + row) * n + e] : 0.0;
+      }
+  } else {
+    load_pair(x + (size_t)e * K.xd, live, K.xd, kq, xb);  // (a tail lane's address is formed, never read)
+    encode<NTL>(K, lds, lane, xb, act);
   }
 }
 

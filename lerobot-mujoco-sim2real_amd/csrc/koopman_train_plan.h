@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/koopman_mpc.h"
+#include "koopman_layout.h"
 
 namespace ktrain {
 
@@ -37,12 +38,12 @@ constexpr int MAXL = 5;         // encoder layers the wave's scratch plan covers
 constexpr int MAXP = 64;        // pre_length
 constexpr int TILE_LD = 18;     // doubles per row of a wave's 16 x 16 transpose tile (see k_koopman_grad)
 constexpr int WAVES = 4;        // waves per workgroup
-constexpr size_t LDS_BYTES = 160 * 1024;
+constexpr size_t LDS_BYTES = KOOPMAN_LDS_BYTES;
 
 struct Plan {
   int xd, ud, nl, outw, nz, ntl, P, npos;
   int width[SIM_KMAXLAYER + 1];
-  int ntile[SIM_KMAXLAYER], ks[SIM_KMAXLAYER], frag[SIM_KMAXLAYER];  // encoder (KDev's)
+  int ntile[SIM_KMAXLAYER], ks[SIM_KMAXLAYER], frag[SIM_KMAXLAYER];  // encoder (klayout::Encoder's)
   int bias, enc_total;                                             // doubles staged in LDS
   int wt[SIM_KMAXLAYER], kst[SIM_KMAXLAYER];                       // W_l' fragments, their k-steps
   int ab, abks, at, atks;
@@ -66,14 +67,8 @@ struct Plan {
 // code with its message in err
 inline int make_plan(const sim_koopman_desc& d, const sim_koopman_train_opts& o, Plan& pl, std::string& err,
                      bool bil = false, int u_z = 0) {
+  if (int rc = klayout::check_desc(d, err)) return rc;
   const int xd = d.x_dim, ud = d.u_dim, nl = d.nlayer;
-  if (xd < 1 || xd > SIM_KMAXX) return err = "x_dim must be in 1..8", SIM_E_MODEL;
-  if (ud < 1 || ud > SIM_KMAXU) return err = "u_dim must be in 1..8", SIM_E_MODEL;
-  if (nl < 2 || nl > SIM_KMAXLAYER) return err = "nlayer must be in 2..6", SIM_E_MODEL;
-  if (d.horizon < 1 || d.horizon > SIM_KMAXH) return err = "horizon must be in 1..32", SIM_E_MODEL;
-  if (d.width[0] != xd) return err = "width[0] must equal x_dim", SIM_E_MODEL;
-  for (int l = 1; l <= nl; l++)
-    if (d.width[l] < 1 || d.width[l] > SIM_KMAXW) return err = "encoder widths must be in 1..64", SIM_E_MODEL;
   if (nl > MAXL)
     return err = "trainer: nlayer must be <= 5 (the scratch plan keeps four hidden layers' activations)",
            SIM_E_MODEL;
@@ -88,23 +83,16 @@ inline int make_plan(const sim_koopman_desc& d, const sim_koopman_train_opts& o,
   pl.xd = xd, pl.ud = ud, pl.nl = nl, pl.outw = d.width[nl], pl.nz = xd + d.width[nl];
   pl.P = o.pre_length, pl.npos = o.npos;
   for (int l = 0; l <= nl; l++) pl.width[l] = d.width[l];
-  int off = 0;
-  for (int l = 0; l < nl; l++) {
-    pl.ntile[l] = l == nl - 1 ? (d.width[l + 1] + 15) / 16 : 4;
-    pl.ks[l] = l == 0 ? 2 : 16;
-    pl.frag[l] = off;
-    off += pl.ntile[l] * pl.ks[l] * 64;
-  }
-  pl.ntl = pl.ntile[nl - 1];
-  pl.bias = off;
-  off += nl * SIM_KMAXW;
-  pl.enc_total = off;
+  const klayout::Encoder enc = klayout::encoder(d);
+  for (int l = 0; l < nl; l++) pl.ntile[l] = enc.ntile[l], pl.ks[l] = enc.ks[l], pl.frag[l] = enc.frag[l];
+  pl.ntl = enc.ntl, pl.bias = enc.bias, pl.enc_total = enc.total;
+  int off = enc.total;
   for (int l = 1; l < nl; l++) {
     pl.kst[l] = 4 * pl.ntile[l];
     pl.wt[l] = off;
     off += 4 * pl.kst[l] * 64;
   }
-  pl.abks = 2 + 4 * pl.ntl + 2, pl.atks = 2 + 4 * pl.ntl;
+  pl.abks = klayout::ks_zu(enc), pl.atks = klayout::ks_z(enc);
   pl.ab = off, off += (1 + pl.ntl) * pl.abks * 64;
   pl.at = off, off += (1 + pl.ntl) * pl.atks * 64;
   if (bil) {
@@ -148,16 +136,11 @@ inline size_t stat_doubles(const Plan& pl, int max_slot) { return (size_t)max_sl
 inline size_t tab_doubles(const Plan& pl) { return (size_t)pl.P * 4 + 8; }
 inline size_t step_bytes(const Plan& pl) { return (STEP_DOUBLES + tab_doubles(pl)) * sizeof(double); }
 
-// lifted-state index of (tile, row in tile) / of padded k index kk; -1 = padding
-inline int z_of_row(const Plan& pl, int tile, int r) {
-  if (tile == 0) return r < pl.xd ? r : -1;
-  const int f = 16 * (tile - 1) + r;
-  return f < pl.outw ? pl.xd + f : -1;
-}
-inline int z_of_k(const Plan& pl, int kk) {
-  if (kk < 8) return kk < pl.xd ? kk : -1;
-  kk -= 8;
-  return (kk < 16 * pl.ntl && kk < pl.outw) ? pl.xd + kk : -1;
+// the padded row and k maps (klayout::z_of_row, z_of_k, u_of_k) read these fields of the plan
+inline klayout::Encoder layout_of(const Plan& pl) {
+  klayout::Encoder e{};
+  e.xd = pl.xd, e.ud = pl.ud, e.nl = pl.nl, e.outw = pl.outw, e.nz = pl.nz, e.ntl = pl.ntl;
+  return e;
 }
 
 // parameter index of H_c[i][j] (bilinear plan)
@@ -184,49 +167,40 @@ inline bool index_map(const Plan& pl, std::vector<int32_t>& map) {
     else
       ok = false;
   };
+  using klayout::each_frag;
+  const klayout::Encoder e = layout_of(pl);
+  auto zrow = [&](int row) { return klayout::z_of_row(e, row >> 4, row & 15); };
   for (int l = 0; l < pl.nl; l++) {
     const int in = pl.width[l], ou = pl.width[l + 1];
-    for (int T = 0; T < pl.ntile[l]; T++)
-      for (int s = 0; s < pl.ks[l]; s++)
-        for (int lane = 0; lane < 64; lane++) {
-          const int row = 16 * T + (lane & 15), col = 4 * s + (lane >> 4);
-          if (row < ou && col < in) put(pl.pw[l] + row * in + col, pl.frag[l] + (T * pl.ks[l] + s) * 64 + lane);
-        }
+    each_frag(pl.ntile[l], pl.ks[l], [&](int pos, int row, int col) {
+      if (row < ou && col < in) put(pl.pw[l] + row * in + col, pl.frag[l] + pos);
+    });
     for (int r = 0; r < ou; r++) put(pl.pb[l] + r, pl.bias + l * SIM_KMAXW + r);
     if (l >= 1)  // W_l': rows = the layer's inputs, k = its outputs
-      for (int T = 0; T < 4; T++)
-        for (int s = 0; s < pl.kst[l]; s++)
-          for (int lane = 0; lane < 64; lane++) {
-            const int row = 16 * T + (lane & 15), k = 4 * s + (lane >> 4);
-            if (row < in && k < ou) put(pl.pw[l] + k * in + row, pl.wt[l] + (T * pl.kst[l] + s) * 64 + lane);
-          }
+      each_frag(4, pl.kst[l], [&](int pos, int row, int k) {
+        if (row < in && k < ou) put(pl.pw[l] + k * in + row, pl.wt[l] + pos);
+      });
   }
-  for (int tile = 0; tile <= pl.ntl; tile++) {
-    for (int s = 0; s < pl.abks; s++)
-      for (int lane = 0; lane < 64; lane++) {
-        const int i = z_of_row(pl, tile, lane & 15), kk = 4 * s + (lane >> 4);
-        const int j = z_of_k(pl, kk), c = kk - (8 + 16 * pl.ntl);
-        const int pos = pl.ab + (tile * pl.abks + s) * 64 + lane;
-        if (i >= 0 && j >= 0) put(pl.pA + i * pl.nz + j, pos);
-        if (i >= 0 && c >= 0 && c < pl.ud) put(pl.pB + i * pl.ud + c, pos);
-      }
-    for (int s = 0; s < pl.atks; s++)
-      for (int lane = 0; lane < 64; lane++) {
-        const int j = z_of_row(pl, tile, lane & 15), i = z_of_k(pl, 4 * s + (lane >> 4));
-        if (i >= 0 && j >= 0) put(pl.pA + i * pl.nz + j, pl.at + (tile * pl.atks + s) * 64 + lane);
-      }
+  for (int tile = 0; tile <= pl.ntl; tile++) {  // (tile by tile: the order decides which copy is map[0])
+    each_frag(1, pl.abks, [&](int pos, int r, int kk) {
+      const int i = klayout::z_of_row(e, tile, r), j = klayout::z_of_k(e, kk), c = klayout::u_of_k(e, kk);
+      if (i >= 0 && j >= 0) put(pl.pA + i * pl.nz + j, pl.ab + tile * pl.abks * 64 + pos);
+      if (i >= 0 && c >= 0) put(pl.pB + i * pl.ud + c, pl.ab + tile * pl.abks * 64 + pos);
+    });
+    each_frag(1, pl.atks, [&](int pos, int r, int kk) {
+      const int j = klayout::z_of_row(e, tile, r), i = klayout::z_of_k(e, kk);
+      if (i >= 0 && j >= 0) put(pl.pA + i * pl.nz + j, pl.at + tile * pl.atks * 64 + pos);
+    });
   }
   if (pl.bil)  // H_c as A's part of ab, H_c' as at: every H parameter has exactly these two copies
     for (int c = 0; c < pl.ud; c++)
-      for (int tile = 0; tile <= pl.ntl; tile++)
-        for (int s = 0; s < pl.atks; s++)
-          for (int lane = 0; lane < 64; lane++) {
-            const int r = z_of_row(pl, tile, lane & 15), k = z_of_k(pl, 4 * s + (lane >> 4));
-            if (r < 0 || k < 0) continue;
-            const int o = ((c * (1 + pl.ntl) + tile) * pl.atks + s) * 64 + lane;
-            put(h_param(pl, c, r, k), pl.hf + o);
-            put(h_param(pl, c, k, r), pl.ht + o);
-          }
+      each_frag(1 + pl.ntl, pl.atks, [&](int pos, int row, int kk) {
+        const int r = zrow(row), k = klayout::z_of_k(e, kk);
+        if (r < 0 || k < 0) return;
+        const int o = c * (1 + pl.ntl) * pl.atks * 64 + pos;
+        put(h_param(pl, c, r, k), pl.hf + o);
+        put(h_param(pl, c, k, r), pl.ht + o);
+      });
   for (int p = 0; p < pl.nparam; p++)
     if (map[p] < 0) ok = false;
   return ok;

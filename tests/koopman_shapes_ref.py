@@ -94,7 +94,7 @@ def dims(row):
 
 
 def bilinear_epw(nz, nu, H):
-    """A RESTATEMENT of sim_koopman_set_bilinear's LDS plan (csrc/koopman_mpc.hip), not a readback:
+    """A RESTATEMENT of sim_koopman_set_bilinear's LDS plan (csrc/koopman_bilinear.hip), not a readback:
     the envs (waves) per workgroup it gives k_bilinear, or 0 where it refuses.  The ABI exposes no
     such figure; the tests need it to pick batch sizes that give one, two and sixteen workgroups."""
     N = H * nu

@@ -1,4 +1,4 @@
-"""The DBKN control step with input limits (csrc/koopman_mpc.hip k_bilinear_box:
+"""The DBKN control step with input limits (csrc/koopman_bilinear.hip k_bilinear_box:
 sim_koopman_set_bilinear_box, sim_koopman_bilinear_box_step; control/koopman.box_plan_bilinear;
 MPCController.set_box_bilinear / step_box_bilinear; KoopmanMPCTracking(constrained=True) on a prepared
 DBKN controller) against a float64 reference that uses no project code.

@@ -1,5 +1,6 @@
-"""The Koopman controller kernels (csrc/koopman_mpc.hip: k_encode, k_feedforward, k_mpc_step,
-k_bilinear, k_predict) across the shapes the ABI accepts, against the float64 oracle.
+"""The Koopman controller kernels (csrc/koopman_mpc.hip: k_encode, k_feedforward, k_mpc_step;
+koopman_bilinear.hip: k_bilinear; koopman_predict.hip: k_predict) across the shapes the ABI accepts,
+against the float64 oracle.
 
 test_koopman_mpc.py and test_koopman_predict.py run the kernels at the reference's shape (encoder
 [8, 64, 64, 64, 64, 24], u_dim 5, horizon 10 or 7) and at [8, 64, 64, 40].  sim_koopman_create takes

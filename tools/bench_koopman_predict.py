@@ -79,7 +79,7 @@ def predict_resusage(path=None):
         rows = json.load(open(path))
     else:
         import resusage
-        rows = resusage.rows(["koopman_mpc.hip"])
+        rows = resusage.rows(["koopman_predict.hip"])
     out = {}
     for r in rows:
         for rl in (0, 1):
@@ -132,7 +132,7 @@ def main():
     a = ap.parse_args()
     if a.dump_resusage:
         import resusage
-        json.dump(resusage.rows(["koopman_mpc.hip"]), open(a.dump_resusage, "w"), indent=1)
+        json.dump(resusage.rows(["koopman_predict.hip"]), open(a.dump_resusage, "w"), indent=1)
         return
     if a.launches < 20:
         ap.error("--launches must be >= 20")

@@ -1,7 +1,8 @@
 // koopman_train_selftest.cpp — the Koopman trainer's host-side code (csrc/koopman_train_plan.h: the
 // plan of the DKUC trainer and of the bilinear DBKN one, the fragment index map, the slot gather index,
-// blob packing, the nmse workspace sizes, the per-step argument checks) as a stand-alone program for the
-// host sanitizers.  No GPU, no HIP:
+// blob packing, the nmse workspace sizes, the per-step argument checks) and the layout every Koopman unit
+// packs by (csrc/koopman_layout.h: the description's checks, the encoder layout, the padded row and k
+// maps, the fragment loop) as a stand-alone program for the host sanitizers.  No GPU, no HIP:
 //
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all
 //       tools/koopman_train_selftest.cpp -o /tmp/koopman_train_selftest && /tmp/koopman_train_selftest
@@ -192,8 +193,112 @@ static void check_bilinear(std::vector<int> w, int ud, int P, int u_z) {
   REQUIRE(make_plan(d, o, pl, err, false, 2) == SIM_OK && !pl.bil);  // (u_z is the bilinear plan's alone)
 }
 
+// koopman_layout.h, which every Koopman unit packs by: the padded row and k maps one-to-one onto the
+// unpadded indices, the fragment loop against its element-wise definition, the encoder layout against
+// the rule restated (and the trainer's plan, where it takes the shape)
+static void check_layout(std::vector<int> w, int ud) {
+  using namespace klayout;
+  const sim_koopman_desc d = desc_of(w, ud);
+  std::string err;
+  REQUIRE(check_desc(d, err) == SIM_OK && err.empty());
+  const Encoder e = encoder(d);
+  const int nl = (int)w.size() - 1, xd = w[0], outw = w[nl], nz = xd + outw;
+  REQUIRE(e.xd == xd && e.ud == ud && e.nl == nl && e.outw == outw && e.nz == nz && e.ntl == (outw + 15) / 16);
+  int off = 0;
+  for (int l = 0; l < nl; l++) {
+    REQUIRE(e.ntile[l] == (l == nl - 1 ? (w[l + 1] + 15) / 16 : 4) && e.ks[l] == (l == 0 ? 2 : 16) && e.frag[l] == off);
+    off += e.ntile[l] * e.ks[l] * 64;
+  }
+  REQUIRE(e.bias == off && e.total == off + nl * SIM_KMAXW && e.total % 2 == 0);
+  REQUIRE(ks_z(e) == 2 + 4 * e.ntl && ks_zu(e) == ks_z(e) + 2);
+  if (nl <= ktrain::MAXL) {
+    ktrain::Plan pl;
+    REQUIRE(ktrain::make_plan(d, opts_of(5, 1), pl, err) == SIM_OK);
+    for (int l = 0; l < nl; l++) REQUIRE(pl.ntile[l] == e.ntile[l] && pl.ks[l] == e.ks[l] && pl.frag[l] == e.frag[l]);
+    REQUIRE(pl.bias == e.bias && pl.enc_total == e.total && pl.ntl == e.ntl && pl.abks == ks_zu(e) && pl.atks == ks_z(e));
+  }
+  // rows: every lifted index once over tiles 0 .. ntl, in order; -1 on the padding and past the tiles
+  std::vector<int> seen(nz, 0);
+  for (int tile = 0; tile <= e.ntl + 1; tile++)
+    for (int r = 0; r < 16; r++) {
+      const int z = z_of_row(e, tile, r);
+      const int want = tile == 0 ? (r < xd ? r : -1) : (tile <= e.ntl && 16 * (tile - 1) + r < outw ? xd + 16 * (tile - 1) + r : -1);
+      REQUIRE(z == want && z < nz);
+      if (z >= 0) seen[z]++;
+    }
+  for (int z = 0; z < nz; z++) REQUIRE(seen[z] == 1);
+  // k: [x (8) | features (16 ntl) | u (8)]; every lifted index and every input once, never both
+  std::vector<int> zs(nz, 0), us(ud, 0);
+  for (int kk = -4; kk < 4 * ks_zu(e) + 8; kk++) {
+    const int z = z_of_k(e, kk), u = u_of_k(e, kk), f = kk - 8, c = kk - 8 - 16 * e.ntl;
+    REQUIRE(z == (kk >= 0 && kk < 8 ? (kk < xd ? kk : -1) : (f >= 0 && f < 16 * e.ntl && f < outw ? xd + f : -1)));
+    REQUIRE(u == (c >= 0 && c < ud ? c : -1) && !(z >= 0 && u >= 0) && z < nz && u < ud);
+    REQUIRE(zu_col(e, kk, 100) == (z >= 0 ? 100 + z : (u >= 0 ? 100 + nz + u : -1)));
+    if (z >= 0) zs[z]++;
+    if (u >= 0) us[u]++;
+  }
+  for (int z = 0; z < nz; z++) REQUIRE(zs[z] == 1);
+  for (int u = 0; u < ud; u++) REQUIRE(us[u] == 1);
+  // the fragment loop: lane l of fragment (T, s) holds element (16 T + (l & 15), 4 s + (l >> 4))
+  for (int l = 0; l < nl; l++) {
+    const int nt = e.ntile[l], ks = e.ks[l];
+    std::vector<double> blob((size_t)nt * ks * 64, -1.0);
+    fill_frag(blob.data(), nt, ks, [](int row, int k) { return 1000.0 * row + k; });
+    for (int T = 0; T < nt; T++)
+      for (int s = 0; s < ks; s++)
+        for (int lane = 0; lane < 64; lane++)
+          REQUIRE(blob[(T * ks + s) * 64 + lane] == 1000.0 * (16 * T + (lane & 15)) + 4 * s + (lane >> 4));
+    std::vector<int> hit(blob.size(), 0);
+    each_frag(nt, ks, [&](int pos, int row, int k) {
+      REQUIRE(pos >= 0 && pos < (int)hit.size() && blob[pos] == 1000.0 * row + k);
+      hit[pos]++;
+    });
+    for (int h : hit) REQUIRE(h == 1);
+  }
+}
+
+static void check_desc_refusals() {
+  using namespace klayout;
+  const sim_koopman_desc good = desc_of({8, 64, 64, 24}, 5);
+  std::string err;
+  auto refused = [&](sim_koopman_desc d, const char* msg) {
+    err.clear();
+    REQUIRE(check_desc(d, err) == SIM_E_MODEL && err == msg);
+  };
+  sim_koopman_desc d = good;
+  d.x_dim = 0, refused(d, "x_dim must be in 1..8");
+  d.x_dim = SIM_KMAXX + 1, refused(d, "x_dim must be in 1..8");
+  d = good, d.u_dim = 0, refused(d, "u_dim must be in 1..8");
+  d.u_dim = SIM_KMAXU + 1, refused(d, "u_dim must be in 1..8");
+  d = good, d.nlayer = 1, refused(d, "nlayer must be in 2..6");
+  d.nlayer = SIM_KMAXLAYER + 1, refused(d, "nlayer must be in 2..6");
+  d = good, d.horizon = 0, refused(d, "horizon must be in 1..32");
+  d.horizon = SIM_KMAXH + 1, refused(d, "horizon must be in 1..32");
+  d = good, d.width[0] = 7, refused(d, "width[0] must equal x_dim");
+  d = good, d.width[2] = 0, refused(d, "encoder widths must be in 1..64");
+  d = good, d.width[3] = SIM_KMAXW + 1, refused(d, "encoder widths must be in 1..64");
+  // the same refusals reach the trainer's plan with their messages
+  ktrain::Plan pl;
+  d = good, d.u_dim = 9;
+  REQUIRE(ktrain::make_plan(d, opts_of(5, 3), pl, err) == SIM_E_MODEL && err == "u_dim must be in 1..8");
+  // the reference's encoder: the figures the kernels were written against
+  const Encoder e = encoder(desc_of({8, 64, 64, 64, 64, 24}, 5));
+  const int frag[5] = {0, 512, 4608, 8704, 12800};
+  for (int l = 0; l < 5; l++) REQUIRE(e.frag[l] == frag[l]);
+  REQUIRE(e.ntl == 2 && e.bias == 14848 && e.total == 15168 && e.nz == 32);
+  REQUIRE(KOOPMAN_LDS_BYTES == 163840 && ktrain::LDS_BYTES == KOOPMAN_LDS_BYTES);
+}
+
 int main() {
   using namespace ktrain;
+  // koopman_layout.h at the widths of the shape table's rows ref, nz45, odd, tiny, deep and nz3
+  check_layout({8, 64, 64, 64, 64, 24}, 5);
+  check_layout({8, 64, 37}, 5);
+  check_layout({7, 33, 17, 22}, 3);
+  check_layout({3, 6, 10}, 1);
+  check_layout({5, 64, 64, 64, 64, 64, 9}, 4);
+  check_layout({2, 1, 1}, 2);
+  check_desc_refusals();
   for (int u_z = 0; u_z < 2; u_z++) {
     check_bilinear({8, 64, 64, 64, 64, 24}, 5, 5, u_z);  // the reference's shape
     check_bilinear({8, 64, 64, 40}, 5, 1, u_z);
