@@ -19,7 +19,7 @@ SOURCES = ["soarm_sim.hip", "soarm_cforce.hip", "koopman_mpc.hip", "koopman_bili
 # translation units compiled for the host only (the CPU backend, the model build: no kernels)
 HOST_ONLY = {"soarm_cpu.hip", "soarm_model.hip"}
 HEADERS = ["dmodel.h", "soarm_kernels.h", "soarm_step.h", "soarm_collide.h", "soarm_pgs.h", "soarm_rs.h", "soarm_newton.h",
-           "soarm_prof.h", "soarm_substep.h",
+           "soarm_prof.h", "soarm_substep.h", "soarm_dense.h",
            "soarm_env.h", "soarm_ikbox.h", "sim_internal.h", "koopman_frag.h", "koopman_layout.h", "koopman_internal.h",
            "koopman_train_plan.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -77,7 +77,8 @@ void dispatch_sol(int sol, F&& f) {
 
 // ---- CPU backend: the same per-env code as the kernels (soarm_step.h, soarm_collide.h,
 // soarm_env.h) compiled for the host, envs split over threads; the constraint solve is a
-// dense fp32 restatement of mj_solPGS / mj_solNewton over MuJoCo's row order.  All pointers
+// dense fp32 restatement of mj_solPGS / mj_solNewton over MuJoCo's row order, on the one
+// statement of the dense rows it shares with the readout's kernel (soarm_dense.h).  All pointers
 // are host memory; calls are synchronous.
 struct CpuBatch;
 int cpu_batch_create(const sim_model* m, int n, CpuBatch** out);

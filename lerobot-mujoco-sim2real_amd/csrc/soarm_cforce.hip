@@ -3,10 +3,12 @@
 // the step's kernels (soarm_sim.hip) sit on their register limit and stay byte for byte what they
 // are; this one shares only the per-env physics headers with them.
 //
-// k_contact_force<NA, NF, SOL> is the dense solve the CPU backend states (soarm_cpu.hip: rows in
-// MuJoCo's order -- dof frictionloss, joint limits lower/upper, 4 pyramid edges per contact in
-// contact order -- solved by mj_solPGS's Gauss-Seidel in that order or mj_solNewton's primal Newton
-// with the exact line search), laid out for the GPU: 16 lanes per env (one DPP row), 4 envs per
+// k_contact_force<NA, NF, SOL> is the dense solve the CPU backend also runs (soarm_cpu.hip), on the
+// one statement of the rows both share (soarm_dense.h: MuJoCo's order -- dof frictionloss, joint
+// limits lower/upper, 4 pyramid edges per contact in contact order -- with the rows' constants, force
+// and cost, the contact frame and Jacobian, the packed Cholesky solve and the pyramid decode), solved
+// by mj_solPGS's Gauss-Seidel in that order or mj_solNewton's primal Newton with the exact line
+// search, laid out for the GPU: 16 lanes per env (one DPP row), 4 envs per
 // wave.  Lane l of an env owns rows r = l (mod 16), one per slot s = r / 16; the slots are unrolled,
 // so a lane's per-row scalars (aref, R, frictionloss, AR diagonal, force) are registers.  The lanes
 // build their rows' Jacobians and W = M^-1 J' in parallel (the bulk of the work) into LDS rows
@@ -24,6 +26,7 @@
 #include "soarm_collide.h"
 #include "soarm_env.h"
 #include "sim_internal.h"
+#include "soarm_dense.h"
 #include "soarm_pgs.h"
 
 using namespace soarm;
@@ -32,7 +35,6 @@ namespace {
 
 constexpr int CF_LPE = 16;            // lanes per env
 constexpr int CF_EPW = 64 / CF_LPE;   // envs per wave (workgroup)
-enum { CROW_NONE = 0, CROW_FRICTION = 1, CROW_LIMIT = 2, CROW_CONTACT = 3 };
 
 template <int NA, int NF>
 struct CfDims {
@@ -43,108 +45,6 @@ struct CfDims {
   static constexpr int ROWF = 2 * NV + 1;                   // J | W, odd stride: the lanes' rows on distinct banks
   static constexpr int NH = NV * (NV + 1) / 2;
 };
-
-constexpr int tri(int i, int k) { return i >= k ? i * (i + 1) / 2 + k : k * (k + 1) / 2 + i; }
-
-// M x with the block-diagonal packed M of Sim (arm NA x NA | one 6x6 per free body)
-template <int NA, int NF>
-DEVI void mul_m(const Sim<NA, NF>& S, const float (&x)[NA + 6 * NF], float (&y)[NA + 6 * NF]) {
-#pragma unroll
-  for (int i = 0; i < NA; i++) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < NA; k++) s += S.MA[tri(i, k)] * x[k];
-    y[i] = s;
-  }
-#pragma unroll
-  for (int f = 0; f < NF; f++) {
-    const int d0 = NA + 6 * f;
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-      float s = 0.f;
-#pragma unroll
-      for (int k = 0; k < 6; k++) s += S.MF[f][tri(i, k)] * x[d0 + k];
-      y[d0 + i] = s;
-    }
-  }
-}
-// element (i, k) of M, i >= k compile-time after unrolling
-template <int NA, int NF>
-DEVI float m_at(const Sim<NA, NF>& S, int i, int k) {
-  if (i < NA) return S.MA[tri(i, k)];
-  const int f = (i - NA) / 6, d0 = NA + 6 * f;
-  return k >= d0 ? S.MF[f][tri(i - d0, k - d0)] : 0.f;
-}
-
-// dense Cholesky solve of the SPD packed H; false on a non-positive pivot (x is then unusable)
-template <int N>
-DEVI bool chol_solve(const float (&A)[N * (N + 1) / 2], float (&x)[N], const float (&b)[N]) {
-  float L[N * (N + 1) / 2];
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < N; i++)
-#pragma unroll
-    for (int j = 0; j <= i; j++) {
-      float s = A[tri(i, j)];
-#pragma unroll
-      for (int k = 0; k < j; k++) s -= L[tri(i, k)] * L[tri(j, k)];
-      if (i == j) {
-        ok = ok && s > 0.f;
-        L[tri(i, i)] = sqrtf(s);
-      } else {
-        L[tri(i, j)] = s / L[tri(j, j)];
-      }
-    }
-  float y[N];
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    float s = b[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) s -= L[tri(i, k)] * y[k];
-    y[i] = s / L[tri(i, i)];
-  }
-#pragma unroll
-  for (int i = N - 1; i >= 0; i--) {
-    float s = y[i];
-#pragma unroll
-    for (int k = i + 1; k < N; k++) s -= L[tri(k, i)] * x[k];
-    x[i] = s / L[tri(i, i)];
-  }
-  return ok;
-}
-
-// row at x = J a - aref: force -s'(x) and whether the row is in its quadratic zone; its cost s(x)
-DEVI float row_force(int type, float R, float fl, float x, bool& quad) {
-  if (type == CROW_FRICTION) {
-    quad = x > -R * fl && x < R * fl;
-    return x <= -R * fl ? fl : x >= R * fl ? -fl : -x / R;
-  }
-  quad = x < 0.f;
-  return quad ? -x / R : 0.f;
-}
-DEVI float row_cost(int type, float R, float fl, float x) {
-  if (type == CROW_FRICTION) {
-    if (x <= -R * fl) return -fl * x - 0.5f * R * fl * fl;
-    if (x >= R * fl) return fl * x - 0.5f * R * fl * fl;
-    return 0.5f * x * x / R;
-  }
-  return x < 0.f ? 0.5f * x * x / R : 0.f;
-}
-
-// contact frame (mju_makeFrame): rows normal, tangent 1, tangent 2
-DEVI void contact_frame(const float nrm[3], float fr[9]) {
-  fr[0] = nrm[0], fr[1] = nrm[1], fr[2] = nrm[2];
-  float y[3];
-  if (fabsf(fr[1]) < 0.5f)
-    y[0] = 0, y[1] = 1, y[2] = 0;
-  else
-    y[0] = 0, y[1] = 0, y[2] = 1;
-  const float dd = dot3(fr, y);
-  y[0] -= dd * fr[0], y[1] -= dd * fr[1], y[2] -= dd * fr[2];
-  const float inv = 1.f / sqrtf(dot3(y, y));
-  fr[3] = y[0] * inv, fr[4] = y[1] * inv, fr[5] = y[2] * inv;
-  cross(fr + 6, fr, fr + 3);
-}
 
 template <int NA, int NF, int SOL>
 __global__ __launch_bounds__(64) void k_contact_force(const DModel* __restrict__ dm, int n, sim_state st,
@@ -198,7 +98,8 @@ __global__ __launch_bounds__(64) void k_contact_force(const DModel* __restrict__
   if (st.qfrc_applied) S.add_applied(st.qfrc_applied, n, e);
   S.solve_m(S.qacc_s, S.fsmooth);
 
-  // ---- the lane's rows (mj_makeConstraint, the constants of make_rows in soarm_cpu.hip)
+  // ---- the lane's rows (mj_makeConstraint: soarm_dense.h states each kind; a lane finds "row r of
+  // the env" by counting the rows before it in MuJoCo's order)
   int type[NSL];
   float aref[NSL], R[NSL], fl[NSL], ARd[NSL], f[NSL];
   float pv[NV];  // PGS: this lane's part of sum_r W_r f_r (the warm start's v)
@@ -212,17 +113,15 @@ __global__ __launch_bounds__(64) void k_contact_force(const DModel* __restrict__
 #pragma unroll
     for (int i = 0; i < NV; i++) J[i] = 0.f;
     // (an absent row: J = 0, aref = 0, R = 1 -- its force stays an exact zero in either solver)
-    type[s] = CROW_NONE, aref[s] = 0.f, R[s] = 1.f, fl[s] = 0.f;
+    type[s] = ROW_NONE, aref[s] = 0.f, R[s] = 1.f, fl[s] = 0.f;
+    auto put = [&](int t, const RowConst& c) { type[s] = t, aref[s] = c.aref, R[s] = c.R, fl[s] = c.fl; };
     int k = 0;
 #pragma unroll
     for (int i = 0; i < NV; i++) {  // dof frictionloss
       if (!(m.dof_frictionloss[i] > 0.f)) continue;
       if (k == r) {
         J[i] = 1.f;
-        type[s] = CROW_FRICTION;
-        aref[s] = -m.dof_fricB[i] * S.qvel[i];
-        R[s] = m.dof_fricR[i];
-        fl[s] = m.dof_frictionloss[i];
+        put(ROW_FRICTION, friction_row(m, i, S.qvel[i]));
       }
       k++;
     }
@@ -234,12 +133,8 @@ __global__ __launch_bounds__(64) void k_contact_force(const DModel* __restrict__
         const float dist = side == 0 ? S.qpos[i] - m.jnt_range[i][0] : m.jnt_range[i][1] - S.qpos[i];
         if (!(dist < m.jnt_margin[i])) continue;
         if (k == r) {
-          const float sg = side == 0 ? 1.f : -1.f;
-          const float imp = impedance(m.jnt_solimp[i], dist, m.jnt_margin[i]);
-          J[i] = sg;
-          type[s] = CROW_LIMIT;
-          aref[s] = -m.jnt_KB[i][1] * (sg * S.qvel[i]) - m.jnt_KB[i][0] * imp * (dist - m.jnt_margin[i]);
-          R[s] = fmaxf(MINVALF, (1.f - imp) * m.dof_invweight0[i] / imp);
+          J[i] = side == 0 ? 1.f : -1.f;
+          put(ROW_LIMIT, limit_row(m, i, side, dist, S.qvel[i]));
         }
         k++;
       }
@@ -252,57 +147,12 @@ __global__ __launch_bounds__(64) void k_contact_force(const DModel* __restrict__
       const float cpos[3] = {con[c * 8 + 1], con[c * 8 + 2], con[c * 8 + 3]};
       const float cn[3] = {con[c * 8 + 4], con[c * 8 + 5], con[c * 8 + 6]};
       const int p = __float_as_int(con[c * 8 + 7]);
-      const int b1 = m.pair_body1[p], b2 = m.pair_body2[p];
       const float mu = S.fric >= 0.f ? S.fric : m.pair_friction[p];
-      float fr[9];
+      float fr[9], jd[3][NV], imp, R0, Rpy;
       contact_frame(cn, fr);
-      // relative translational Jacobian (body2 - body1) at the contact point, contact frame
-      float jd[3][NV];
-#pragma unroll
-      for (int q = 0; q < 3; q++)
-#pragma unroll
-        for (int i = 0; i < NV; i++) jd[q][i] = 0.f;
-#pragma unroll
-      for (int side = 0; side < 2; side++) {
-        const int b = side ? b2 : b1;
-        const float sg = side ? 1.f : -1.f;
-#pragma unroll
-        for (int i = 0; i < NA; i++)
-          if (b >= i + 2 && b < 2 + NA) {  // hinge i moves chain bodies i+2.. (reference point: origin)
-            float l[3];
-            cross(l, S.cdof[i], cpos);
-            const float jp[3] = {S.cdof[i][3] + l[0], S.cdof[i][4] + l[1], S.cdof[i][5] + l[2]};
-#pragma unroll
-            for (int q = 0; q < 3; q++) jd[q][i] += sg * dot3(fr + 3 * q, jp);
-          }
-#pragma unroll
-        for (int fb_ = 0; fb_ < NF; fb_++) {
-          const int fb = 2 + NA + fb_, d0 = NA + 6 * fb_;
-          if (b != fb) continue;
-          const float off[3] = {cpos[0] - S.xpos[fb][0], cpos[1] - S.xpos[fb][1], cpos[2] - S.xpos[fb][2]};
-#pragma unroll
-          for (int i = 0; i < 6; i++) {
-            float l[3];
-            cross(l, S.cdof[d0 + i], off);
-            const float jp[3] = {S.cdof[d0 + i][3] + l[0], S.cdof[d0 + i][4] + l[1], S.cdof[d0 + i][5] + l[2]};
-#pragma unroll
-            for (int q = 0; q < 3; q++) jd[q][d0 + i] += sg * dot3(fr + 3 * q, jp);
-          }
-        }
-      }
-      const float imp = impedance(m.pair_solimp[p], cdist, m.pair_margin[p]);
-      const float tran = m.pair_tran[p];
-      const float R0 = fmaxf(MINVALF, (1.f - imp) * (tran + mu * mu * tran) / imp);
-      const float sgn = (ed & 1) ? -mu : mu;
-      float vel = 0.f;
-#pragma unroll
-      for (int i = 0; i < NV; i++) {
-        J[i] = jd[0][i] + sgn * ((ed >> 1) ? jd[2][i] : jd[1][i]);
-        vel += J[i] * S.qvel[i];
-      }
-      type[s] = CROW_CONTACT;
-      aref[s] = -m.pair_KB[p][1] * vel - m.pair_KB[p][0] * imp * (cdist - m.pair_margin[p]);
-      R[s] = 2.f * mu * mu * R0 / m.impratio;
+      contact_jac(S, m.pair_body1[p], m.pair_body2[p], cpos, fr, jd);
+      contact_consts(m, p, mu, cdist, imp, R0, Rpy);
+      put(ROW_CONTACT, {edge_row(m, jd, ed, mu, S.qvel, p, imp, cdist, J), Rpy, 0.f});
     }
     S.solve_m(W, J);
     float jw = 0.f, jar = -aref[s];
@@ -314,11 +164,7 @@ __global__ __launch_bounds__(64) void k_contact_force(const DModel* __restrict__
       rows[r * ROWF + NV + i] = W[i];
     }
     ARd[s] = jw + R[s];
-    // PGS's warm start: the forces implied by qacc_warmstart
-    if (type[s] == CROW_FRICTION)
-      f[s] = jar <= -fl[s] * R[s] ? fl[s] : jar >= fl[s] * R[s] ? -fl[s] : -jar / R[s];
-    else
-      f[s] = type[s] != CROW_NONE && jar < 0.f ? -jar / R[s] : 0.f;
+    f[s] = warm_force(type[s], R[s], fl[s], jar);  // PGS's warm start: the forces implied by qacc_warmstart
 #pragma unroll
     for (int i = 0; i < NV; i++) pv[i] += W[i] * f[s];
   }
@@ -376,8 +222,8 @@ __global__ __launch_bounds__(64) void k_contact_force(const DModel* __restrict__
 #pragma unroll
           for (int i = 0; i < NV; i++) res += Jr[i] * v[i];
           float fn = f[s] - res / ARd[s];
-          fn = type[s] == CROW_FRICTION ? fminf(fmaxf(fn, -fl[s]), fl[s]) : fmaxf(fn, 0.f);
-          const bool mine = lane == q && !done && type[s] != CROW_NONE;
+          fn = pgs_project(type[s], fl[s], fn);
+          const bool mine = lane == q && !done && type[s] != ROW_NONE;
           const float dfo = mine ? fn - f[s] : 0.f;
           const float df = __shfl(dfo, q, CF_LPE);
           if (mine && dfo != 0.f) {
@@ -484,9 +330,9 @@ __global__ __launch_bounds__(64) void k_contact_force(const DModel* __restrict__
         float* const bps = s_bp[col];  // [r] the row's first breakpoint | [NROW + r] a frictionloss row's second
 #pragma unroll
         for (int s = 0; s < NSL; s++) {
-          const bool fric = type[s] == CROW_FRICTION;
+          const bool fric = type[s] == ROW_FRICTION;
           float b0 = INFINITY, b1 = INFINITY;
-          if (type[s] != CROW_NONE && jv[s] != 0.f) {
+          if (type[s] != ROW_NONE && jv[s] != 0.f) {
             const float al0 = ((fric ? -R[s] * fl[s] : 0.f) - jar[s]) / jv[s], al1 = (R[s] * fl[s] - jar[s]) / jv[s];
             if (al0 > 0.f) b0 = al0;
             if (fric && al1 > 0.f) b1 = al1;
@@ -551,7 +397,7 @@ __global__ __launch_bounds__(64) void k_contact_force(const DModel* __restrict__
 
   // ---- mju_decodePyramid per contact (lane c takes contact c)
 #pragma unroll
-  for (int s = 0; s < NSL; s++) s_fe[col][lane + CF_LPE * s] = type[s] != CROW_NONE ? f[s] : 0.f;
+  for (int s = 0; s < NSL; s++) s_fe[col][lane + CF_LPE * s] = type[s] != ROW_NONE ? f[s] : 0.f;
   __syncthreads();
   static_assert(SIM_MAXCON <= CF_LPE, "one lane per contact");
   if (live && lane < SIM_MAXCON) {
@@ -563,12 +409,7 @@ __global__ __launch_bounds__(64) void k_contact_force(const DModel* __restrict__
       const float cn[3] = {con[c * 8 + 4], con[c * 8 + 5], con[c * 8 + 6]};
       float fr[9];
       contact_frame(cn, fr);
-      const float* g = &s_fe[col][nr - 4 * ncon + 4 * c];
-      fo[0] = (g[0] + g[1]) + (g[2] + g[3]);
-      fo[1] = mu * (g[0] - g[1]);
-      fo[2] = mu * (g[2] - g[3]);
-#pragma unroll
-      for (int q = 0; q < 3; q++) fo[3 + q] = fo[0] * fr[q] + fo[1] * fr[3 + q] + fo[2] * fr[6 + q];
+      decode_pyramid(&s_fe[col][nr - 4 * ncon + 4 * c], mu, fr, fo);
     }
 #pragma unroll
     for (int q = 0; q < 6; q++) force[((size_t)e * SIM_MAXCON + c) * 6 + q] = fo[q];

@@ -11,7 +11,11 @@
 // the rows are built densely in MuJoCo's order (dof frictionloss, joint limits lower/upper,
 // contacts x 4 pyramid edges; mj_makeConstraint) and solved by a scalar fp32 restatement of
 // mj_solPGS (Gauss-Seidel in row order, the scaled-improvement stop) or mj_solNewton (primal
-// Newton, exact line search), the model's `solver`.  Envs are split over host threads
+// Newton, exact line search), the model's `solver`.  The rows themselves -- their constants, force
+// and cost, the contact frame and Jacobian, M's packed blocks, the packed Cholesky solve, the
+// pyramid decode -- are stated once in soarm_dense.h, which the contact-force readout's kernel
+// (soarm_cforce.hip) shares; this file keeps the enumeration (each contact's Jacobian once, then its
+// 4 edges) and the serial solver loops.  Envs are split over host threads
 // (SOARM_CPU_THREADS, else OMP_NUM_THREADS, else all cores); every env is independent, so the
 // result does not depend on the thread count.
 //
@@ -21,11 +25,13 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <thread>
 #include <vector>
 
 #include "sim_internal.h"
 #include "soarm_collide.h"
+#include "soarm_dense.h"
 #include "soarm_env.h"
 #include "soarm_ikbox.h"
 
@@ -72,6 +78,12 @@ void parallel_envs(int n, F&& f) {
 struct CpuContact {
   float dist, pos[3], n[3];
   int pair;
+  // the 8-float record of sim_contacts / sim_contact_forces: dist, pos, normal, pair id as bits
+  void record(float* o) const {
+    o[0] = dist;
+    for (int q = 0; q < 3; q++) o[1 + q] = pos[q], o[4 + q] = n[q];
+    memcpy(o + 7, &pair, 4);
+  }
 };
 
 template <int NA, int NF>
@@ -100,8 +112,7 @@ int collide_env(const CpuBatch& B, Sim<NA, NF>& S, int e, CpuContact* con, int& 
 }
 
 // ------------------------------------------------------------------ constraint rows
-enum { ROW_FRICTION = 0, ROW_LIMIT = 1, ROW_CONTACT = 2 };
-
+// (the row kinds, their constants, the contact frame and Jacobian: soarm_dense.h)
 template <int NA, int NF>
 struct Rows {
   static constexpr int NV = NA + 6 * NF;
@@ -109,120 +120,41 @@ struct Rows {
   int nr = 0;
   int type[MAXR];
   float J[MAXR][NV], aref[MAXR], R[MAXR], fl[MAXR];
+  // appends a row of the given kind and constants with J = 0; returns its index
+  int add(int t, const RowConst& c) {
+    const int r = nr++;
+    type[r] = t, aref[r] = c.aref, R[r] = c.R, fl[r] = c.fl;
+    for (int k = 0; k < NV; k++) J[r][k] = 0.f;
+    return r;
+  }
 };
 
-// contact frame (mju_makeFrame): rows normal, tangent 1, tangent 2
-inline void contact_frame(const float* nrm, float fr[9]) {
-  fr[0] = nrm[0], fr[1] = nrm[1], fr[2] = nrm[2];
-  float y[3];
-  if (fabsf(fr[1]) < 0.5f)
-    y[0] = 0, y[1] = 1, y[2] = 0;
-  else
-    y[0] = 0, y[1] = 0, y[2] = 1;
-  const float dd = dot3(fr, y);
-  y[0] -= dd * fr[0], y[1] -= dd * fr[1], y[2] -= dd * fr[2];
-  const float inv = 1.f / sqrtf(dot3(y, y));
-  fr[3] = y[0] * inv, fr[4] = y[1] * inv, fr[5] = y[2] * inv;
-  cross(fr + 6, fr, fr + 3);
-}
-
-// mj_makeConstraint in MuJoCo's row order, from the same model constants as the kernels
-// (soarm_pgs.h solve_constraints: dof_fricR/B, jnt_KB, pair_KB / tran / solimp / margin)
+// mj_makeConstraint in MuJoCo's row order: each contact's frame and Jacobian once, then its 4 edges
 template <int NA, int NF>
 void make_rows(const Sim<NA, NF>& S, const CpuContact* con, int ncon, Rows<NA, NF>& X) {
   constexpr int NV = Sim<NA, NF>::NV;
   const DModel& m = *S.mp;
-  int r = 0;
-  for (int i = 0; i < NV; i++) {  // dof frictionloss
-    if (!(m.dof_frictionloss[i] > 0.f)) continue;
-    for (int k = 0; k < NV; k++) X.J[r][k] = k == i ? 1.f : 0.f;
-    X.type[r] = ROW_FRICTION;
-    X.aref[r] = -m.dof_fricB[i] * S.qvel[i];
-    X.R[r] = m.dof_fricR[i];
-    X.fl[r] = m.dof_frictionloss[i];
-    r++;
-  }
+  X.nr = 0;
+  for (int i = 0; i < NV; i++)  // dof frictionloss
+    if (m.dof_frictionloss[i] > 0.f) X.J[X.add(ROW_FRICTION, friction_row(m, i, S.qvel[i]))][i] = 1.f;
   for (int i = 0; i < NA; i++) {  // joint limits, lower then upper
     if (!m.jnt_limited[i]) continue;
     for (int side = 0; side < 2; side++) {
       const float dist = side == 0 ? S.qpos[i] - m.jnt_range[i][0] : m.jnt_range[i][1] - S.qpos[i];
-      if (!(dist < m.jnt_margin[i])) continue;
-      const float sg = side == 0 ? 1.f : -1.f;
-      const float imp = impedance(m.jnt_solimp[i], dist, m.jnt_margin[i]);
-      for (int k = 0; k < NV; k++) X.J[r][k] = k == i ? sg : 0.f;
-      X.type[r] = ROW_LIMIT;
-      X.aref[r] = -m.jnt_KB[i][1] * (sg * S.qvel[i]) - m.jnt_KB[i][0] * imp * (dist - m.jnt_margin[i]);
-      X.R[r] = fmaxf(MINVALF, (1.f - imp) * m.dof_invweight0[i] / imp);
-      X.fl[r] = 0.f;
-      r++;
+      if (dist < m.jnt_margin[i]) X.J[X.add(ROW_LIMIT, limit_row(m, i, side, dist, S.qvel[i]))][i] = side == 0 ? 1.f : -1.f;
     }
   }
   for (int c = 0; c < ncon; c++) {  // contacts: 4 pyramid edges each (condim 3)
     const CpuContact& cc = con[c];
-    const int p = cc.pair, b1 = m.pair_body1[p], b2 = m.pair_body2[p];
+    const int p = cc.pair;
     const float mu = S.fric >= 0.f ? S.fric : m.pair_friction[p];
-    float fr[9];
+    float fr[9], jd[3][NV], imp, R0, Rpy;
     contact_frame(cc.n, fr);
-    // relative translational Jacobian (body2 - body1) at the contact point, contact frame
-    float jd[3][NV] = {};
-    for (int side = 0; side < 2; side++) {
-      const int b = side ? b2 : b1;
-      const float sg = side ? 1.f : -1.f;
-      for (int i = 0; i < NA; i++)
-        if (b >= i + 2 && b < 2 + NA) {  // hinge i moves chain bodies i+2.. (reference point: origin)
-          float l[3];
-          cross(l, S.cdof[i], cc.pos);
-          const float jp[3] = {S.cdof[i][3] + l[0], S.cdof[i][4] + l[1], S.cdof[i][5] + l[2]};
-          for (int q = 0; q < 3; q++) jd[q][i] += sg * dot3(fr + 3 * q, jp);
-        }
-      for (int f = 0; f < NF; f++) {
-        const int fb = 2 + NA + f, d0 = NA + 6 * f;
-        if (b != fb) continue;
-        const float off[3] = {cc.pos[0] - S.xpos[fb][0], cc.pos[1] - S.xpos[fb][1], cc.pos[2] - S.xpos[fb][2]};
-        for (int i = 0; i < 6; i++) {
-          float l[3];
-          cross(l, S.cdof[d0 + i], off);
-          const float jp[3] = {S.cdof[d0 + i][3] + l[0], S.cdof[d0 + i][4] + l[1], S.cdof[d0 + i][5] + l[2]};
-          for (int q = 0; q < 3; q++) jd[q][d0 + i] += sg * dot3(fr + 3 * q, jp);
-        }
-      }
-    }
-    const float imp = impedance(m.pair_solimp[p], cc.dist, m.pair_margin[p]);
-    const float tran = m.pair_tran[p];
-    const float R0 = fmaxf(MINVALF, (1.f - imp) * (tran + mu * mu * tran) / imp);
-    const float Rpy = 2.f * mu * mu * R0 / m.impratio;
+    contact_jac(S, m.pair_body1[p], m.pair_body2[p], cc.pos, fr, jd);
+    contact_consts(m, p, mu, cc.dist, imp, R0, Rpy);
     for (int ed = 0; ed < 4; ed++) {
-      const float s = (ed & 1) ? -mu : mu;
-      const float* jt = jd[1 + (ed >> 1)];
-      float vel = 0.f;
-      for (int k = 0; k < NV; k++) {
-        X.J[r][k] = jd[0][k] + s * jt[k];
-        vel += X.J[r][k] * S.qvel[k];
-      }
-      X.type[r] = ROW_CONTACT;
-      X.aref[r] = -m.pair_KB[p][1] * vel - m.pair_KB[p][0] * imp * (cc.dist - m.pair_margin[p]);
-      X.R[r] = Rpy;
-      X.fl[r] = 0.f;
-      r++;
-    }
-  }
-  X.nr = r;
-}
-
-// M x with the block-diagonal packed M of Sim (arm NA x NA | one 6x6 per free body)
-template <int NA, int NF>
-void mul_m(const Sim<NA, NF>& S, const float* x, float* y) {
-  for (int i = 0; i < NA; i++) {
-    float s = 0.f;
-    for (int k = 0; k < NA; k++) s += S.MA[i >= k ? i * (i + 1) / 2 + k : k * (k + 1) / 2 + i] * x[k];
-    y[i] = s;
-  }
-  for (int f = 0; f < NF; f++) {
-    const int d0 = NA + 6 * f;
-    for (int i = 0; i < 6; i++) {
-      float s = 0.f;
-      for (int k = 0; k < 6; k++) s += S.MF[f][i >= k ? i * (i + 1) / 2 + k : k * (k + 1) / 2 + i] * x[d0 + k];
-      y[d0 + i] = s;
+      const int r = X.add(ROW_CONTACT, {0.f, Rpy, 0.f});
+      X.aref[r] = edge_row(m, jd, ed, mu, S.qvel, p, imp, cc.dist, X.J[r]);
     }
   }
 }
@@ -245,12 +177,7 @@ void solve_pgs(Sim<NA, NF>& S, const Rows<NA, NF>& X, float* frow = nullptr) {
   for (int r = 0; r < nr; r++) {
     float jar = -X.aref[r];
     for (int i = 0; i < NV; i++) jar += X.J[r][i] * S.warm[i];
-    if (X.type[r] == ROW_FRICTION) {
-      const float fl = X.fl[r];
-      f[r] = jar <= -fl * X.R[r] ? fl : jar >= fl * X.R[r] ? -fl : -jar / X.R[r];
-    } else {
-      f[r] = jar < 0.f ? -jar / X.R[r] : 0.f;
-    }
+    f[r] = warm_force(X.type[r], X.R[r], X.fl[r], jar);
   }
   for (int i = 0; i < NV; i++) v[i] = S.qacc_s[i];
   for (int r = 0; r < nr; r++)
@@ -272,8 +199,7 @@ void solve_pgs(Sim<NA, NF>& S, const Rows<NA, NF>& X, float* frow = nullptr) {
     for (int r = 0; r < nr; r++) {
       float res = -X.aref[r] + X.R[r] * f[r];
       for (int i = 0; i < NV; i++) res += X.J[r][i] * v[i];
-      float fn = f[r] - res / ARd[r];
-      fn = X.type[r] == ROW_FRICTION ? fminf(fmaxf(fn, -X.fl[r]), X.fl[r]) : fmaxf(fn, 0.f);
+      const float fn = pgs_project(X.type[r], X.fl[r], f[r] - res / ARd[r]);
       const float df = fn - f[r];
       if (df != 0.f) {
         for (int i = 0; i < NV; i++) v[i] += W[r][i] * df;
@@ -294,30 +220,7 @@ void solve_pgs(Sim<NA, NF>& S, const Rows<NA, NF>& X, float* frow = nullptr) {
 }
 
 // ------------------------------------------------------------------ mj_solNewton
-// row r at x = J_r a - aref_r: force -s_r'(x) and whether the row is in its quadratic zone
-template <int NA, int NF>
-float row_force(const Rows<NA, NF>& X, int r, float x, bool& quad) {
-  const float R = X.R[r];
-  if (X.type[r] == ROW_FRICTION) {
-    const float fl = X.fl[r];
-    quad = x > -R * fl && x < R * fl;
-    return x <= -R * fl ? fl : x >= R * fl ? -fl : -x / R;
-  }
-  quad = x < 0.f;
-  return quad ? -x / R : 0.f;
-}
-template <int NA, int NF>
-float row_cost(const Rows<NA, NF>& X, int r, float x) {
-  const float R = X.R[r];
-  if (X.type[r] == ROW_FRICTION) {
-    const float fl = X.fl[r];
-    if (x <= -R * fl) return -fl * x - 0.5f * R * fl * fl;
-    if (x >= R * fl) return fl * x - 0.5f * R * fl * fl;
-    return 0.5f * x * x / R;
-  }
-  return x < 0.f ? 0.5f * x * x / R : 0.f;
-}
-
+// (a row's force and cost at x = J_r a - aref_r: row_force / row_cost, soarm_dense.h)
 template <int NA, int NF>
 struct NewtonCtx {
   static constexpr int NV = Sim<NA, NF>::NV, MAXR = Rows<NA, NF>::MAXR;
@@ -333,7 +236,7 @@ struct NewtonCtx {
       float x = -X.aref[r];
       for (int i = 0; i < NV; i++) x += X.J[r][i] * a[i];
       jar[r] = x;
-      c += row_cost(X, r, x);
+      c += row_cost(X.type[r], X.R[r], X.fl[r], x);
     }
     return c;
   }
@@ -342,7 +245,7 @@ struct NewtonCtx {
     float g = g0 + alpha * pMp, h = pMp;
     for (int r = 0; r < X.nr; r++) {
       bool q;
-      g -= row_force(X, r, jar[r] + alpha * jv[r], q) * jv[r];
+      g -= row_force(X.type[r], X.R[r], X.fl[r], jar[r] + alpha * jv[r], q) * jv[r];
       if (q) h += jv[r] * jv[r] / X.R[r];
     }
     if (curv) *curv = h;
@@ -379,35 +282,6 @@ struct NewtonCtx {
   }
 };
 
-// dense Cholesky solve of the SPD H (n x n, row-major n x n); false on a non-positive pivot
-template <int N>
-bool chol_solve(float (&A)[N][N], float* x, const float* b) {
-  float L[N][N];
-  for (int i = 0; i < N; i++)
-    for (int j = 0; j <= i; j++) {
-      float s = A[i][j];
-      for (int k = 0; k < j; k++) s -= L[i][k] * L[j][k];
-      if (i == j) {
-        if (!(s > 0.f)) return false;
-        L[i][i] = sqrtf(s);
-      } else {
-        L[i][j] = s / L[j][j];
-      }
-    }
-  float y[N];
-  for (int i = 0; i < N; i++) {
-    float s = b[i];
-    for (int k = 0; k < i; k++) s -= L[i][k] * y[k];
-    y[i] = s / L[i][i];
-  }
-  for (int i = N - 1; i >= 0; i--) {
-    float s = y[i];
-    for (int k = i + 1; k < N; k++) s -= L[k][i] * x[k];
-    x[i] = s / L[i][i];
-  }
-  return true;
-}
-
 template <int NA, int NF>
 void solve_newton(Sim<NA, NF>& S, const Rows<NA, NF>& X, float* frow = nullptr) {
   constexpr int NV = Sim<NA, NF>::NV, MAXR = Rows<NA, NF>::MAXR;
@@ -420,23 +294,19 @@ void solve_newton(Sim<NA, NF>& S, const Rows<NA, NF>& X, float* frow = nullptr) 
   for (int i = 0; i < NV; i++) a[i] = cw < cs ? S.warm[i] : S.qacc_s[i];
   float cost = C.cost(a, jar);
   for (int it = 0; it < m.iterations; it++) {
-    float da[NV], g[NV], H[NV][NV];
+    float da[NV], g[NV], H[NV * (NV + 1) / 2];  // H = M + J' D J, packed lower triangle
     for (int i = 0; i < NV; i++) da[i] = a[i] - S.qacc_s[i];
     mul_m(S, da, g);
-    for (int k = 0; k < NV; k++) {  // H = M (columns of the packed blocks)
-      float e[NV] = {}, Me[NV];
-      e[k] = 1.f;
-      mul_m(S, e, Me);
-      for (int i = 0; i < NV; i++) H[i][k] = Me[i];
-    }
+    for (int i = 0; i < NV; i++)
+      for (int k = 0; k <= i; k++) H[tri(i, k)] = m_at(S, i, k);
     for (int r = 0; r < X.nr; r++) {
       bool q;
-      const float f = row_force(X, r, jar[r], q);
+      const float f = row_force(X.type[r], X.R[r], X.fl[r], jar[r], q);
       for (int i = 0; i < NV; i++) g[i] -= X.J[r][i] * f;
       if (q) {
         const float D = 1.f / X.R[r];
         for (int i = 0; i < NV; i++)
-          for (int k = 0; k < NV; k++) H[i][k] += D * X.J[r][i] * X.J[r][k];
+          for (int k = 0; k <= i; k++) H[tri(i, k)] += D * X.J[r][i] * X.J[r][k];
       }
     }
     float gn = 0.f;
@@ -469,7 +339,8 @@ void solve_newton(Sim<NA, NF>& S, const Rows<NA, NF>& X, float* frow = nullptr) 
     bool same = true;
     for (int r = 0; r < X.nr; r++) {
       bool q0, q1;
-      const float f0 = row_force(X, r, jar[r], q0), f1 = row_force(X, r, jn[r], q1);
+      const float f0 = row_force(X.type[r], X.R[r], X.fl[r], jar[r], q0);
+      const float f1 = row_force(X.type[r], X.R[r], X.fl[r], jn[r], q1);
       same = same && q0 == q1 && (q0 || f0 == f1);
     }
     for (int i = 0; i < NV; i++) a[i] = an[i];
@@ -480,7 +351,7 @@ void solve_newton(Sim<NA, NF>& S, const Rows<NA, NF>& X, float* frow = nullptr) 
   for (int i = 0; i < NV; i++) S.qacc[i] = a[i], S.fcon[i] = 0.f;
   for (int r = 0; r < X.nr; r++) {
     bool q;
-    const float f = row_force(X, r, jar[r], q);
+    const float f = row_force(X.type[r], X.R[r], X.fl[r], jar[r], q);
     for (int i = 0; i < NV; i++) S.fcon[i] += X.J[r][i] * f;
     if (frow) frow[r] = f;  // efc_force as MuJoCo derives it from qacc
   }
@@ -571,17 +442,31 @@ int check(const CpuBatch* c, const sim_state* s) {
 
 // ===================================================================== entry points
 int cpu_batch_create(const sim_model* m, int n, CpuBatch** out) {
-  CpuBatch* c = new CpuBatch();
+  auto c = std::make_unique<CpuBatch>();
   c->model = m;
   c->n = n;
   c->dm = bind_tables(*m, m->hull_rec.data(), m->hull_lutrec.data(), m->hull_ovf.data(), m->hull_sb.data());
   c->prec = pair_records(c->dm);
   if (!m->desc.disable_contact) c->sepax.assign((size_t)std::max(m->desc.npair, 1) * 3 * n, 0.f);
-  *out = c;
+  *out = c.release();
   return SIM_OK;
 }
 
 void cpu_batch_free(CpuBatch* c) { delete c; }
+
+namespace {
+// a one-env batch for a single call, freed on every way out of the caller's scope
+struct BatchFree {
+  void operator()(CpuBatch* c) const { cpu_batch_free(c); }
+};
+using TempBatch = std::unique_ptr<CpuBatch, BatchFree>;
+int temp_batch(const sim_model* m, TempBatch& out) {
+  CpuBatch* c = nullptr;
+  const int rc = cpu_batch_create(m, 1, &c);
+  out.reset(c);
+  return rc;
+}
+}  // namespace
 
 // the contacts at qpos0 into m->dm.c0_* (dmodel.h): kinematics at qpos0, then every candidate pair
 // through the kernels' collide code, as k_collide writes them (mask bit per pair with contacts,
@@ -591,8 +476,8 @@ int cpu_qpos0_contacts(sim_model* m) {
   memset(d.c0_w, 0, sizeof(d.c0_w));
   d.c0_n = 0;
   if (m->desc.disable_contact || d.npair == 0) return SIM_OK;
-  CpuBatch* c = nullptr;
-  cpu_batch_create(m, 1, &c);
+  TempBatch c;
+  if (int rc = temp_batch(m, c)) return rc;
   const int nw = (d.npair + 31) >> 5;
   dispatch_nf(m->nf, [&](auto nfc) {
     constexpr int NF = decltype(nfc)::value;
@@ -614,7 +499,6 @@ int cpu_qpos0_contacts(sim_model* m) {
       }
     }
   });
-  cpu_batch_free(c);
   return SIM_OK;
 }
 
@@ -622,14 +506,13 @@ extern "C" int soarm_test_hull_support(const sim_model* m, int g, const float* d
   if (!m || !dirs || !out || nd < 0) return soarm_set_error(SIM_E_ARG, "null argument");
   if (g < 0 || g >= m->desc.ngeom || m->desc.geom_type[g] != SIM_GEOM_MESH || m->lutadr[g] < 0)
     return soarm_set_error(SIM_E_ARG, "not a mesh geom");
-  CpuBatch* c = nullptr;
-  cpu_batch_create(m, 1, &c);
+  TempBatch c;
+  if (int rc = temp_batch(m, c)) return rc;
   const GeomRec G = geom_rec_make(c->dm, g);
   for (int i = 0; i < nd; i++) {
     const float3 v = hull_support(G, dirs + 3 * i);
     out[3 * i] = v.x, out[3 * i + 1] = v.y, out[3 * i + 2] = v.z;
   }
-  cpu_batch_free(c);
   return SIM_OK;
 }
 
@@ -695,12 +578,7 @@ int cpu_contacts(CpuBatch* c, const sim_state* s, float* out, int32_t* ncon) {
       CpuContact cl[SIM_MAXCON];
       int status = 0;
       const int nc = collide_env(*c, S, e, cl, status);
-      for (int k = 0; k < nc; k++) {
-        float* o = out + ((size_t)e * SIM_MAXCON + k) * 8;
-        o[0] = cl[k].dist;
-        for (int q = 0; q < 3; q++) o[1 + q] = cl[k].pos[q], o[4 + q] = cl[k].n[q];
-        memcpy(o + 7, &cl[k].pair, 4);
-      }
+      for (int k = 0; k < nc; k++) cl[k].record(out + ((size_t)e * SIM_MAXCON + k) * 8);
       ncon[e] = nc;
     });
   });
@@ -742,16 +620,8 @@ int cpu_contact_forces(CpuBatch* c, const sim_state* s, const sim_params& pp, fl
         const float mu = S.fric >= 0.f ? S.fric : m.pair_friction[cl[k].pair];
         float fr[9];
         contact_frame(cl[k].n, fr);
-        const float* g = edge + 4 * k;
-        fo[0] = (g[0] + g[1]) + (g[2] + g[3]);
-        fo[1] = mu * (g[0] - g[1]);
-        fo[2] = mu * (g[2] - g[3]);
-        for (int q = 0; q < 3; q++) fo[3 + q] = fo[0] * fr[q] + fo[1] * fr[3 + q] + fo[2] * fr[6 + q];
-        if (co) {
-          co[0] = cl[k].dist;
-          for (int q = 0; q < 3; q++) co[1 + q] = cl[k].pos[q], co[4 + q] = cl[k].n[q];
-          memcpy(co + 7, &cl[k].pair, 4);
-        }
+        decode_pyramid(edge + 4 * k, mu, fr, fo);
+        if (co) cl[k].record(co);
       }
       ncon[e] = nc;
     });

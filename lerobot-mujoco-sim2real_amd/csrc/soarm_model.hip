@@ -449,7 +449,7 @@ int sim_model_create(const sim_model_desc* desc, const float* hull_vert, const i
   if (int rc = hull_climb_records(M.get(), hull_vert, hull_adr, hull_adj)) return rc;
   hull_support_bounds(M.get(), hull_vert);
   hull_cell_records(M.get(), lut);
-  cpu_qpos0_contacts(M.get());  // (the hull tables above are its input)
+  if (int rc = cpu_qpos0_contacts(M.get())) return rc;  // (the hull tables above are its input)
   *out = M.release();
   return SIM_OK;
 }
